@@ -8,10 +8,12 @@ faces (periodic), exterior stencil, swap. Every GPU holds exactly 512^3 cells (-
 the NodeAware partitioner's MaxLink choice for the xGMI mesh (1x1xN slabs: two faces per GPU, each on its own
 link); --grid cbrt runs the reference's cube rule (512 * N^0.33333 per axis: 645/813/1024 for N=2/4/8) and
 --partition interface the reference's cut rule.
-Secondary numbers in the JSON line: the halo-exchange GB/s of an exchange-only loop on the same decomposition
-(bin/bench_exchange.cu definition: aggregate halo bytes / time).
+A plain run does what the headline needs and nothing else: set up, warm up (with the fused-triple schedule choice),
+time exactly --steps steps, write --dump-outputs, print the JSON line. --full adds the secondary sections to the same
+line: the halo-exchange GB/s of an exchange-only loop on the same decomposition (bin/bench_exchange.cu definition:
+aggregate halo bytes / time), the same steps with every halo copied (extra.with_exchange) and the per-transport sweep.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   N>1 runs one rank per GPU. Under torch.distributed.run (WORLD_SIZE set) it must equal WORLD_SIZE; without a
   launcher, bench.py itself spawns N fresh child ranks (stencil2_amd/launch.py, loaded by path) before importing
   torch or touching the GPU, waits for them with a bounded timeout, stops every sibling when one fails and exits with
@@ -366,6 +368,14 @@ def build_args(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--per-gpu", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also run the secondary sections: the exchange-only loops (extra.halo_"
+                         "exchange_*), the steps with every halo copied (--with-exchange) and the per-transport sweep "
+                         "(--transport-sweep). Without it they are skipped and their entries are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loop write every rank's field as the timed steps left it (the interior a "
+                         "caller of run() reads) to DIR/u_rank<r>.npy, float32; at most 48 MB over all ranks: a larger "
+                         "field is sampled at fixed seeded cells (dump_outputs)")
     ap.add_argument("--cpu", action="store_true",
                     help="host backend, no GPU (BASELINE config 1's CPU path; the CPU tests of this script)")
     ap.add_argument("--exchange-iters", type=int, default=20)
@@ -378,7 +388,7 @@ def build_args(argv=None):
                     help="the sweeps read the periodic image along axes the decomposition leaves whole (no self-copy "
                          "of those halos); 0 = copy every halo")
     ap.add_argument("--with-exchange", choices=["auto", "on", "off"], default="auto",
-                    help="after the headline, time the same steps with every halo copied (BASELINE config 2 as "
+                    help="--full: after the headline, time the same steps with every halo copied (BASELINE config 2 as "
                          "defined: intra-GPU pack/unpack + compute, the reference's exchange() every iteration) -> "
                          "extra.gcells_with_exchange (auto: on unless --wrap 0 already copies every halo)")
     ap.add_argument("--shared-halo-line", type=int, default=-1,
@@ -431,9 +441,9 @@ def build_args(argv=None):
                     help="seconds of warm-up tuning (transport + overlap choice, agreed over ranks): once spent, the "
                          "remaining candidates are skipped and the fastest timed so far is kept (config.phases_s)")
     ap.add_argument("--transport-sweep", choices=["auto", "on", "off"], default="auto",
-                    help="after the headline: exchange-only GB/s of every transport set on the same decomposition, the "
-                         "reference-rule cube, config 4's 8-quantity radius-3 exchange and the single-process "
-                         "PeerCopy run (auto: only with N > 1)")
+                    help="--full, after the headline: exchange-only GB/s of every transport set on the same "
+                         "decomposition, the reference-rule cube, config 4's 8-quantity radius-3 exchange and the "
+                         "single-process PeerCopy run (auto: only with N > 1)")
     ap.add_argument("--sweep-budget", type=float, default=60.0,
                     help="seconds after which the transport sweep starts no further entry")
     ap.add_argument("--sweep-deadline", type=float, default=240.0,
@@ -546,6 +556,46 @@ def exchange_trimean(env, dd, iters: int, xbytes: int) -> dict:
             "min_ms": round(stats.min() * 1e3, 4)}
 
 
+RUN_GRAPH_STEPS = 1008  # 56 hipGraph blocks of 18 steps: whole pairs and triples, under prepare()'s 1024-step limit
+
+
+def run_lengths(steps: int) -> list:
+    """The run() calls that make up `steps` timed steps. StencilModel.prepare records a whole run as one graph up to
+    1024 steps, so a longer loop is enqueued as runs of RUN_GRAPH_STEPS plus the remainder: the same sweeps in the
+    same order as one run(steps), one graph launch per 1008 steps."""
+    return [RUN_GRAPH_STEPS] * (steps // RUN_GRAPH_STEPS) + [steps % RUN_GRAPH_STEPS] * (steps % RUN_GRAPH_STEPS > 0)
+
+
+def run_steps(model, steps: int):
+    for k in run_lengths(steps):
+        model.run(k)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: all ranks together
+DUMP_SEED = 7
+
+
+def dump_outputs(torch, model, directory: str, rank: int, world: int) -> dict:
+    """--dump-outputs: this rank's interior (z, y, x) as the timed loop left it -> DIR/u_rank<r>.npy (float32). The
+    initial condition and the number of steps before this point depend on the arguments alone, so equal arguments give
+    equal inputs. A field over this rank's share of DUMP_BYTES is written as a 1-D sample: the cells at the sorted
+    flat interior indices numpy.random.default_rng(DUMP_SEED + rank).integers(0, cells, share // 4)."""
+    import numpy as np
+
+    u = model.interior(0)
+    cells = u.numel()
+    keep = DUMP_BYTES // world // 4
+    if cells > keep:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, cells, keep))).to(u.device)
+        nz, ny, nx = u.shape
+        u = u[idx // (ny * nx), idx // nx % ny, idx % nx]
+    a = u.detach().to("cpu", torch.float32).contiguous().numpy()
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, f"u_rank{rank}.npy")
+    np.save(path, a)
+    return {"file": path, "shape": list(a.shape), "cells": int(cells), "sampled": bool(cells > keep)}
+
+
 def main(argv=None):
     args = build_args(argv)
     rc = rank_setup(args.gpus, args.launch_timeout, sys.argv[1:] if argv is None else list(argv))
@@ -603,7 +653,7 @@ def main(argv=None):
         model.init()
         # hipGraph capture + instantiation (no steps run) outside the timed region: the 18-step blocks, and one graph of
         # a whole run(--steps) (the blocks plus the remainder in one launch; the same kernels in the same order)
-        model.prepare([args.steps])
+        model.prepare(sorted(set(run_lengths(args.steps))))
         model.run(args.warmup)
         model.synchronize()
         env.barrier()
@@ -778,7 +828,7 @@ def main(argv=None):
                 best[c] = min(best.get(c, float("inf")), timed_run(model, 18))
         choice = min(best, key=best.get) if best else scands[0]
         model.set_triple_schedule(choice[0], choice[1], 0)
-        model.prepare([args.steps])
+        model.prepare(sorted(set(run_lengths(args.steps))))
         model.run(args.warmup)
         model.synchronize()
         env.barrier()
@@ -795,7 +845,7 @@ def main(argv=None):
     # ---- the timed loop: exactly --steps steps, bracketed by a barrier + device synchronize on both sides ----
     env.barrier()
     t0 = time.perf_counter()
-    model.run(args.steps)  # every step is enqueued; whole blocks of steps replay as one hipGraph where possible
+    run_steps(model, args.steps)  # every step is enqueued; whole blocks of steps replay as one hipGraph where possible
     model.synchronize()
     env.sync()
     elapsed = time.perf_counter() - t0
@@ -806,15 +856,23 @@ def main(argv=None):
     cells = grid[0] * grid[1] * grid[2]
     gcells = cells * args.steps / elapsed / 1e9
 
-    # exchange-only loops on the same decomposition (halo-exchange GB/s, bench_exchange definition)
-    t_ph = time.perf_counter()
+    dumped = None
+    if args.dump_outputs:
+        t_ph = time.perf_counter()
+        dumped = dump_outputs(torch, model, args.dump_outputs, rank, world)
+        ph.mark("dump_outputs", t_ph)
+
+    # --full: exchange-only loops on the same decomposition (halo-exchange GB/s, bench_exchange definition)
     dd = model.domain
-    dd.set_comm_max_blocks(0)  # the exchange alone may use the whole GPU (the overlapped steps confine it to 8 CUs)
     xbytes = int(dd.exchange_bytes_for_method(st.MethodFlags.All))
-    colo_log = colo and topt.completion != topt.Completion.StreamOp and not args.cpu
-    xrec = time_exchanges(env, dd, args.exchange_iters, xbytes, log=colo_log)
-    xrec.update(exchange_trimean(env, dd, args.exchange_iters, xbytes))
-    ph.mark("exchange_loops", t_ph)
+    xrec = {}
+    if args.full:
+        t_ph = time.perf_counter()
+        dd.set_comm_max_blocks(0)  # the exchange alone may use the whole GPU (the overlapped steps confine it to 8 CUs)
+        colo_log = colo and topt.completion != topt.Completion.StreamOp and not args.cpu
+        xrec = time_exchanges(env, dd, args.exchange_iters, xbytes, log=colo_log)
+        xrec.update(exchange_trimean(env, dd, args.exchange_iters, xbytes))
+        ph.mark("exchange_loops", t_ph)
 
     pdim = dd.placement_dim()
     wrap_axes = "".join(c for i, c in enumerate("xyz") if model.wrap_axes() >> i & 1) or "none"
@@ -854,21 +912,22 @@ def main(argv=None):
                    "radius": 1, "parallelism": f"domain-decomp{n}",
                    **model_cfg,
                    "build": st.build_info()["git_sha"]},
-        "extra": {"halo_exchange_GBps": xrec["GBps"], "halo_exchange_stream_GBps": xrec.get("stream_GBps"),
+        "extra": {"full": args.full, "dumped": dumped,
+                  "halo_exchange_GBps": xrec.get("GBps"), "halo_exchange_stream_GBps": xrec.get("stream_GBps"),
                   "halo_exchange_trimean_GBps": xrec.get("trimean_GBps"),
-                  "halo_bytes_per_exchange": xbytes, "exchange_ms": xrec["exchange_ms"],
+                  "halo_bytes_per_exchange": xbytes, "exchange_ms": xrec.get("exchange_ms"),
                   "exchange_trimean_ms": xrec.get("trimean_ms"),
                   "gcells_per_gpu": round(gcells / n, 3), "colo_kernels_us": xrec.get("colo_kernels_us"),
                   "gcells_with_exchange": None, "with_exchange": None,
-                  "transports": "pending" if (args.transport_sweep == "on" or
-                                              (args.transport_sweep == "auto" and world > 1)) else None},
+                  "transports": "pending" if args.full and (args.transport_sweep == "on" or
+                                                            (args.transport_sweep == "auto" and world > 1)) else None},
     }
 
     # BASELINE config 2 as the reference times it (bin/jacobi3d.cu:265-346: exchange() every iteration): the same
     # steps with every halo copied -- the intra-GPU pack/unpack (same-GPU copy-plan kernel) plus the compute kernels
     # (fused triples reading x from 3-deep halos where the layout allows). A failure here costs this entry, not the
     # headline
-    if args.with_exchange == "on" or (args.with_exchange == "auto" and wrap_axes != "none"):
+    if args.full and (args.with_exchange == "on" or (args.with_exchange == "auto" and wrap_axes != "none")):
         t_ph = time.perf_counter()
         m2 = None
         try:
@@ -884,7 +943,7 @@ def main(argv=None):
                 m2.synchronize()
             env.barrier()
             t = time.perf_counter()
-            m2.run(args.steps)
+            run_steps(m2, args.steps)
             m2.synchronize()
             env.sync()
             el = env.agreed_max(time.perf_counter() - t)

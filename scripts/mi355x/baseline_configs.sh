@@ -4,7 +4,7 @@
 # Usage (gpurun): bash scripts/mi355x/baseline_configs.sh <outdir>
 export STENCIL_SKIP_BUILD=1 STENCIL_PLAN_FILE=0 PYTHONPATH=$GRAFT_REPO_ROOT TMPDIR=/tmp
 source scripts/mi355x/steps.sh "${1:-baseline_configs}"
-step c2_bench 120 python bench.py --steps 20 --warmup 5
+step c2_bench 120 python bench.py --steps 20 --warmup 5 --full
 step app_jacobi_t2 200 ./build/bin/jacobi3d 512 512 512 -n 20 --temporal 2
 step app_jacobi_t1 200 ./build/bin/jacobi3d 512 512 512 -n 20
 step c3_bench_exchange 300 ./build/bin/bench_exchange --x 512 --y 512 --z 512 --fr 2 --iters 30

@@ -94,16 +94,19 @@ def test_bench_alltoallv_and_measure_buf_exchange():
     assert re.search(r"^round \d+: 0>0 [0-9.]+ms/[0-9.]+MiB", out, re.M), out[-2000:]
 
 
-def test_bench_py_json_contract():
-    """bench.py on one GPU prints one JSON line with the driver's fields (exact 512^3 grid, fused triples)."""
+def test_bench_py_json_contract(tmp_path):
+    """bench.py on one GPU prints one JSON line with the driver's fields (exact 512^3 grid, fused triples); the plain
+    run stops after the timed loop, and --dump-outputs writes a seeded float32 sample of the 512^3 field."""
     import json
     import sys
+
+    import numpy as np
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2",
-                        "--exchange-iters", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=100, cwd=REPO)
+                        "--exchange-iters", "2", "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=100, cwd=REPO)
     assert p.returncode == 0, p.stdout[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-3000:]
@@ -113,3 +116,8 @@ def test_bench_py_json_contract():
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["value"] > 0
     assert d["config"]["grid"] == [512, 512, 512] and d["config"]["temporal"] == 3
+    assert d["extra"]["with_exchange"] is None and d["extra"]["halo_exchange_GBps"] is None
+    assert "exchange_loops" not in d["config"]["phases_s"]
+    u = np.load(tmp_path / "u_rank0.npy")
+    assert d["extra"]["dumped"]["sampled"] and u.dtype == np.float32 and u.shape == (48 * 2 ** 20 // 4,)
+    assert np.isfinite(u).all() and u.min() < 0.5 < u.max()

@@ -2,9 +2,9 @@
 
 * A rank stuck before RCCL creation (TransportOptions.stall_rccl_init_rank) costs the wait timeout, not a hang: the
   non-blocking creation is abandoned, every RCCL channel falls back to host-staged, and the halos are still exact.
-* bench.py prints its headline before the transport sweep and again after it; an RCCL entry whose communicator never
-  forms records an error and the run still ends with exit 0; the with-exchange figure (config 2 as defined) and the
-  single-process PeerCopy / config-4 Astaroth entries are present.
+* bench.py --full prints its headline before the transport sweep and again after it; an RCCL entry whose communicator
+  never forms records an error and the run still ends with exit 0; the with-exchange figure (config 2 as defined) and
+  the single-process PeerCopy / config-4 Astaroth entries are present.
 """
 import json
 import os
@@ -74,7 +74,7 @@ def test_bench_two_lines_and_stalled_rccl_entry():
     env["STENCIL_RCCL_STALL_RANK"] = "0"
     env["STENCIL_PLAN_FILE"] = "0"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--per-gpu", "128", "--steps", "4",
-                        "--warmup", "2", "--exchange-iters", "4", "--transport-sweep", "on"],
+                        "--warmup", "2", "--exchange-iters", "4", "--full", "--transport-sweep", "on"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -86,6 +86,36 @@ def test_bench_two_lines_and_stalled_rccl_entry():
     assert tr["peer_store"]["devices_used"] == 1 and "GBps" in tr["peer_store"], tr["peer_store"]
     assert "GBps" in tr["peer_engine"], tr["peer_engine"]
     assert tr["astaroth_q8"]["decomposition"] == "1x1x1" and tr["astaroth_q8"]["GBps"] > 0
+
+
+def test_bench_steps_beyond_one_run_graph(st, tmp_path):
+    """--steps over prepare()'s 1024-step whole-run graph: the timed loop is enqueued as runs of 1008 steps plus the
+    remainder (bench.run_lengths), really makes --steps steps, and leaves bitwise the field one unprepared
+    run(warm-up + steps) of the same model leaves (64^3: the dump is the whole field)."""
+    import numpy as np
+
+    import bench
+
+    steps, warm, n = 2100, 2, 64
+    assert bench.run_lengths(steps) == [1008, 1008, 84] and bench.run_lengths(1008) == [1008]
+    assert bench.run_lengths(20) == [20] and bench.run_lengths(1025) == [1008, 17]
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    env["STENCIL_PLAN_FILE"] = "0"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--per-gpu", str(n), "--steps", str(steps),
+                        "--warmup", str(warm), "--schedule-rounds", "0", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][-1]
+    assert d["steps"] == steps and d["ms_per_step"] > 0
+    got = np.load(tmp_path / "u_rank0.npy")
+    assert got.shape == (n, n, n) and not d["extra"]["dumped"]["sampled"]
+    m = st.Jacobi3D((n, n, n), gpus=[0], temporal=3)
+    m.init()
+    m.run(warm + steps)
+    m.synchronize()
+    assert np.array_equal(got, m.interior(0).cpu().numpy())
 
 
 def test_bench_triple_schedule_phase():

@@ -327,8 +327,12 @@ public:
   void set_send_gate(uint64_t *counter, uint64_t target);
   // every halo of this process's one device leaves through fused pack-kernel stores of the Colocated transport
   // (no same-GPU translate for these skip axes, no DMA-engine pipes, no RCCL / staged channels): the only kind of
-  // exchange a producer gate can start early
-  bool gated_send_supported(int skipAxes) const;
+  // exchange a producer gate can start early. withTranslate: same-GPU translate copies are allowed too (fused
+  // triples that read x from halos keep their x self copies in the exchange). They read every plane of the
+  // producer's output, which the gate does not certify, so a gated exchange runs them last on the comm stream, behind
+  // the producers' record_ready events (which the caller must then have recorded) - the co-located sends and
+  // receives still start on the published boundary planes
+  bool gated_send_supported(int skipAxes, bool withTranslate = false) const;
   void swap();
 
   // ---- transport log (wait vs copy of the fused co-located kernels) ----

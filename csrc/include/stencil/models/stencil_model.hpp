@@ -124,7 +124,7 @@ public:
   bool can_pipeline() const { return pipeOk_; }
   // 4 = pipelined triples: fused triples that publish their boundary z planes early, each depth-3 exchange gated on
   // them and running beside the rest of the sweep
-  bool can_pipeline_triples() const { return pipeOk_ && triplesOk_; }
+  bool can_pipeline_triples() const { return pipe3Ok_ && triplesOk_; }
   // CUs the overlapped sweeps leave to the transport kernels (StencilTune::x2reserve); synchronizes first
   void set_comm_reserve(int cus);
   // the fused triples' lockstep schedule (StencilTune x3sphw / x3left / x3parts: launch geometry only, results are
@@ -135,7 +135,7 @@ public:
   bool forwarding() const { return forward_; }
   bool temporal_blocking() const { return pairs_; }
   // three steps per sweep (stencil7x3): temporal >= 3, device sub-domains of 512-cell fp32 rows wrapped in-kernel or of
-  // 512-cell fp32 / 256-cell fp64 columns with x halos
+  // 512-cell fp32 / 256-cell fp64 columns with x halos (the last column may be partial: ragged x extents)
   bool temporal_triples() const { return triples_; }
   int wrap_axes() const { return pairTune_.wrap; } // axes the fused pairs wrap in-kernel (mask 1=x 2=y 4=z)
   int step_wrap_axes() const { return stepTune_.wrap; } // same for single steps (stencil7_apply)
@@ -160,6 +160,7 @@ private:
   bool overlapToggle_ = false;
   bool slabsAfter_ = false; // overlap mode 2 (see set_overlap_mode)
   bool pipeOk_ = false;      // overlap mode 3 possible (see init)
+  bool pipe3Ok_ = false;     // overlap mode 4 possible where triples are (see init)
   bool pipelined_ = false;   // overlap mode 3
   bool pipelined3_ = false;  // overlap mode 4
   int pubDepth_ = 2;         // boundary z planes a sweep publishes at each face (the exchange's z depth)

@@ -707,6 +707,14 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("kind"), py::arg("spheres"), py::arg("stream"),
       py::arg("tune"), py::call_guard<py::gil_scoped_release>());
+  m.def(
+      "stencil7x3_supported",
+      [](DistributedDomain &dd, size_t di, int64_t q, const StencilTune &tune) {
+        // whether stencil7x3_apply would run on the sub-domain's compute region with tune.wrap's axes read in-kernel
+        const LocalDomain &d = dd.domains().at(di);
+        return stencil7x3_supported(d, q, d.get_compute_region(), tune);
+      },
+      py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("tune"));
   m.def("stencil7x2_supported",
         [](DistributedDomain &dd, size_t di, int64_t q) { return stencil7x2_supported(dd.domains().at(di), q); },
         py::arg("dd"), py::arg("domain"), py::arg("qi"));

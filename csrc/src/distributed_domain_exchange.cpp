@@ -388,14 +388,14 @@ void DistributedDomain::set_send_gate(uint64_t *counter, uint64_t target) {
   impl_->gateTarget = target;
 }
 
-bool DistributedDomain::gated_send_supported(int skipAxes) const {
+bool DistributedDomain::gated_send_supported(int skipAxes, bool withTranslate) const {
   if (!realized_ || backend_ != Backend::Device) return false;
   const Impl &I = *impl_;
   if (I.devs.size() != 1 || !I.pipes.empty() || I.rccl) return false;
   const DevCtx &ctx = I.devs[0];
   if (skipAxes != 0 && skipAxes != I.skipAxes) return false;
   const SegList &tl = skipAxes != 0 ? ctx.translateSkip : ctx.translate;
-  if (!tl.host[0].empty() || !tl.host[1].empty()) return false;
+  if (!withTranslate && (!tl.host[0].empty() || !tl.host[1].empty())) return false;
   if (!ctx.stagedSend.empty() || !ctx.stagedRecv.empty() || !ctx.rcclSend.empty() || !ctx.rcclRecv.empty())
     return false;
   return !ctx.coloSend.empty() && topt_.coloCopy == TransportOptions::Copy::Store && topt_.fuseFlags &&
@@ -456,7 +456,10 @@ void DistributedDomain::exchange_async(hipStream_t stream, int skipAxes) {
   const uint64_t gateTarget = I.gateTarget;
   I.gateCounter = nullptr;
   if (gated)
-    STENCIL_REQUIRE(!over && gated_send_supported(skipAxes), "gated exchange without a fused co-located-only plan");
+    STENCIL_REQUIRE(!over && gated_send_supported(skipAxes, true), "gated exchange without a fused co-located-only plan");
+  // gated with same-GPU translate copies: those read every plane of the producers' output, so they run last, behind
+  // the producers' ready events (step 5b); the events pending now are the ones to wait for
+  const std::vector<bool> readyAtGate = I.readyPending;
   // (0) dependencies: the comm streams start after every local domain's producer work
   if (!over && !gated) {
     bool anyMissing = false;
@@ -554,6 +557,7 @@ void DistributedDomain::exchange_async(hipStream_t stream, int skipAxes) {
     TraceRange t("kernel/peer translate");
     const SegList &tl = skipAxes != 0 ? ctx.translateSkip : ctx.translate;
     ctx.translateEmpty = tl.host[parity].empty();
+    if (gated && !ctx.translateEmpty) continue; // deferred behind the producers (5b)
     if (!ctx.translateEmpty) tl.run_device(parity, S(ctx), translateBlocks_);
     if (!over) ctx.translated.record(S(ctx)); // events only matter across streams
   }
@@ -809,6 +813,21 @@ void DistributedDomain::exchange_async(hipStream_t stream, int skipAxes) {
     ctx.coloUnpack.run_device(cv, S(ctx), commBlocks_);
     signal_flags(credits, I.epoch, S(ctx));
   }
+
+  // (5b) gated exchange: the same-GPU translate copies, once the producers' whole kernels are done
+  if (gated)
+    for (auto &ctx : I.devs) {
+      if (ctx.translateEmpty) continue;
+      HIP_CHECK(hipSetDevice(ctx.dev));
+      TraceRange t("kernel/peer translate (after the producers)");
+      for (size_t di = 0; di < domains_.size(); ++di) {
+        STENCIL_REQUIRE(readyAtGate[di], "gated exchange with translate copies needs record_ready of domain " << di);
+        I.ready[di].wait_on(S(ctx));
+      }
+      const SegList &tl = skipAxes != 0 ? ctx.translateSkip : ctx.translate;
+      tl.run_device(parity, S(ctx), translateBlocks_);
+      ctx.translated.record(S(ctx));
+    }
 
   // (6) halos written by peer devices of this process
   for (auto &ctx : I.devs) {

@@ -3,7 +3,10 @@
 //   * stencil7x3_wrap_kernel - whole periodic rows (x wrapped in-kernel, fp32 rows of exactly 512 cells): the
 //     x-neighbours and the wrap are DPP lane rotates of the wave's own registers, nothing is read beyond the row (the
 //     one-GPU headline);
-//   * stencil7x3_xh_kernel - columns with x halos (fp32 x a multiple of 512, fp64 of 256): the same two-chunk lane
+//   * stencil7x3_xh_kernel - columns with x halos (CW = 512 fp32 / 256 fp64 cells; any x extent >= 3 whose last column
+//     holds r = CW or r <= CW - 3 cells: a partial last column finds the row's 3 halo cells inside its own chunks, see
+//     RAG at the kernel; r = CW - 2 and CW - 1, where part of that halo falls outside the wave's chunks, are refused by
+//     stencil7x3_supported and keep the fused pairs): the same two-chunk lane
 //     layout per column of CW cells; only the 3 cells beyond each column end come from outside the wave. The two edge
 //     waves (rows 0 and 11, which otherwise only load and publish their source row) carry the column ends of all 12
 //     rows - wave 0 the left end, wave 11 the right, lane r = row r: one 16-B load per row and plane (cells x-3 .. x /
@@ -125,8 +128,22 @@ __device__ __forceinline__ double x3_row_prev(double v) {
 }
 
 // Columns with x halos (the XH form): every x-neighbour beyond a column end comes from the exchanged halos. BIG:
-// fields of 4 GiB or more (a buffer resource per plane); else one resource over the field, the plane in soffset
-template <typename T, int KIND, bool BIG, bool PUB>
+// fields of 4 GiB or more (a buffer resource per plane); else one resource over the field, the plane in soffset.
+// RAG: a ragged row, whose last column holds a.xr < CW cells (a.xr <= CW - 3: the 3 halo cells beyond the row end lie
+// inside the wave's own chunks and are loaded like interior cells; u1 is then right through cell xr + 1, u2 through
+// xr, u3 through xr - 1, the cone the right edge wave evaluates at a whole column's end). In that column
+//   * a chunk wholly beyond cell xr + 2 loads the last chunk the row still holds instead (the row offset, a
+//     per-segment constant VGPR, is clamped: nothing is read beyond the row pitch) and every cell beyond xr + 2 is
+//     replaced by 1 when its plane is first used (dead lanes stay away from div6v's tiny-sum branch, and whatever the
+//     row padding holds, NaN included, reaches no sum);
+//   * the right edge wave reads the 4 cells xr - 1 .. xr + 2 (inside the row) and publishes values only dead cells use;
+//   * a chunk wholly beyond the row stores into the sink (as rows past the y end), the chunk that straddles the row
+//     end stores its cells inside the row one by one (and the whole chunk into the sink: the same 16-B stores on
+//     every path); nothing outside the compute region is written;
+//   * a published boundary plane counts xr cells.
+// Whole columns of a ragged row run the same kernel with xr = CW; rows of whole columns run the RAG = false
+// instances, which are compiled exactly as before
+template <typename T, int KIND, bool BIG, bool PUB, bool RAG>
 __global__ __launch_bounds__(64 * 12, 3) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
   constexpr bool XH = true;
@@ -218,7 +235,16 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
         const int yw = ywrap(y);
         const int xcol = a.x0 + bx * CW; // first cell of the column
         const int xb = xcol + lane * V;  // chunk h at xb + h * CS
-        const uint32_t rowoff = uint32_t((yw * int64_t(a.px) + xb) * int64_t(sizeof(T)));
+        // RAG: the column's cells inside the row, and per lane the row's cells from its chunk 0 on (chunk h: rel - h CS)
+        const int xr = RAG && bx == a.gx - 1 ? a.xr : CW;
+        const bool ragcol = RAG && xr < CW; // block-uniform
+        const int rel = xr - lane * V;
+        // RAG: chunks beyond the one holding cell xr + 2 (the last halo cell) load that chunk
+        const int clast = ((xr + 2) / V) * V;
+        const uint32_t rowoff =
+            uint32_t((yw * int64_t(a.px) + (RAG ? xcol + min(lane * V, clast) : xb)) * int64_t(sizeof(T)));
+        const uint32_t rowoff1 =
+            RAG ? uint32_t((yw * int64_t(a.px) + xcol + min(lane * V + CS, clast)) * int64_t(sizeof(T))) : 0u;
         const uint32_t outoff = uint32_t((y * int64_t(a.px) + xb) * int64_t(sizeof(T)));
         // XH edge waves: lane r holds row r's 4 cells from x-3 (wave 0) / x+CW-1 (wave 11): the two cells beyond the
         // end (e[1], e[2]) and their outer and inner x-neighbours (e[0], e[3])
@@ -227,7 +253,7 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
         const int ey = yblk - 3 + er;
         const int eyh = (ey - a.hy) * (ey - a.hy), eyc = (ey - a.cy) * (ey - a.cy); // Jacobi spheres, edge lanes
         const uint32_t edgeoff =
-            uint32_t((ywrap(ey) * int64_t(a.px) + (eside ? xcol + CW - 1 : xcol - 3)) * int64_t(sizeof(T)));
+            uint32_t((ywrap(ey) * int64_t(a.px) + (eside ? xcol + (RAG ? xr : CW) - 1 : xcol - 3)) * int64_t(sizeof(T)));
 
         // spheres (Jacobi): a cell (x, y, P) is in the hot sphere iff (x - hx)^2 < Dh = yh - (P - hz)^2 with
         // yh = r1sq - (y - hy)^2 (per segment), in the cold one likewise; the row-plane has no sphere cell when both
@@ -332,13 +358,27 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
                                                         0x00020000)
                     : srcRsrc;
 #pragma unroll
-            for (int h = 0; h < H; ++h) C[k][h] = x3_load16<NV>(rs, rowoff + uint32_t(h * CS * int(sizeof(T))), po);
+            for (int h = 0; h < H; ++h)
+              C[k][h] = x3_load16<NV>(rs, RAG ? (h == 0 ? rowoff : rowoff1) : rowoff + uint32_t(h * CS * int(sizeof(T))),
+                                      po);
             if constexpr (EDGE) {
               if constexpr (sizeof(T) == 4) {
                 E[k] = x3_load16<E4>(rs, edgeoff, po);
               } else {
                 const NV lo = x3_load16<NV>(rs, edgeoff, po), hi = x3_load16<NV>(rs, edgeoff + 16, po);
                 E[k] = E4{lo[0], lo[1], hi[0], hi[1]};
+              }
+            }
+          };
+          // RAG, a ragged column: the cells beyond the row's 3 halo cells become 1 (applied when a plane is first used,
+          // a step after its load was issued, so the lookahead stays in flight)
+          auto live_fix = [&](NV(&c)[H]) {
+            if constexpr (RAG) {
+              if (ragcol) {
+#pragma unroll
+                for (int h = 0; h < H; ++h)
+#pragma unroll
+                  for (int e = 0; e < V; ++e) c[h][e] = h * CS + e - 3 < rel ? c[h][e] : T(1);
               }
             }
           };
@@ -350,6 +390,8 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
             const int zw = z0 - 3 * dz;
 #pragma unroll
             for (int k = 0; k < NC - 1; ++k) load_row(zw + k * dz, k);
+            live_fix(C[0]);
+            live_fix(C[1]); // slot 2: at the first step
 #pragma unroll
             for (int h = 0; h < H; ++h) {
               cs[0][w][h][lane] = C[1][h];
@@ -373,6 +415,7 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
             const int z = z0 + t * dz;
             const int nbuf = buf ^ 1;
             load_row(z + NC * dz, sn);
+            live_fix(C[s2]); // loaded last step, first used here
             NV o[H];
             // every level reads the previous step's rows (buf) and publishes into the other buffer (its readers
             // finished last step) right after its update
@@ -414,15 +457,42 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
               sphere_row(row_sph(z), o);
               // unconditional: a row past the region's y end (the last row group) stores into a per-device sink, so
               // every path has the same vector-memory ops and the next step's load wait counts past these stores
-              char *dp = outRow ? reinterpret_cast<char *>(a.dst + int64_t(z) * a.pxy) + outoff
-                                : a.sink + lane * V * int(sizeof(T));
+              if constexpr (!RAG) {
+                char *dp = outRow ? reinterpret_cast<char *>(a.dst + int64_t(z) * a.pxy) + outoff
+                                  : a.sink + lane * V * int(sizeof(T));
 #pragma unroll
-              for (int h = 0; h < H; ++h) {
-                NV *q = reinterpret_cast<NV *>(dp + h * CS * int(sizeof(T)));
-                if (a.nt)
-                  __builtin_nontemporal_store(o[h], q);
-                else
-                  *q = o[h];
+                for (int h = 0; h < H; ++h) {
+                  NV *q = reinterpret_cast<NV *>(dp + h * CS * int(sizeof(T)));
+                  if (a.nt)
+                    __builtin_nontemporal_store(o[h], q);
+                  else
+                    *q = o[h];
+                }
+              } else {
+                // a chunk with cells beyond the row end goes to the sink too (rel: per-segment); the cells of the
+                // straddling chunk that lie inside the row are then stored one by one (at most one lane per row)
+                char *pd = reinterpret_cast<char *>(a.dst + int64_t(z) * a.pxy) + outoff;
+                char *ps = a.sink + lane * V * int(sizeof(T));
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                  NV *q = reinterpret_cast<NV *>((outRow && rel - h * CS >= V ? pd : ps) + h * CS * int(sizeof(T)));
+                  if (a.nt)
+                    __builtin_nontemporal_store(o[h], q);
+                  else
+                    *q = o[h];
+                }
+                if (ragcol && outRow) {
+#pragma unroll
+                  for (int h = 0; h < H; ++h) {
+                    const int n = rel - h * CS; // cells of the row in this chunk
+                    if (n > 0 && n < V) {
+                      T *qe = reinterpret_cast<T *>(pd + h * CS * int(sizeof(T)));
+#pragma unroll
+                      for (int e = 0; e < V - 1; ++e)
+                        if (e < n) qe[e] = o[h][e];
+                    }
+                  }
+                }
               }
             }
             if constexpr (LV < 1)
@@ -473,7 +543,7 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
             if (pubStep && lane == 0 && w == 0) {
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
               const unsigned long long cells =
-                  (unsigned long long)(min(YO, a.hiy - yblk)) * (unsigned long long)(XH ? CW : a.hix - a.lox);
+                  (unsigned long long)(min(YO, a.hiy - yblk)) * (unsigned long long)(XH ? (RAG ? xr : CW) : a.hix - a.lox);
               __hip_atomic_fetch_add(a.pub, cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             buf = nbuf;
@@ -832,6 +902,15 @@ template <typename T, int KIND> static const void *x3_wrap_kernel_ptr() {
   else
     return nullptr;
 }
+// the XH instance: fields of 4 GiB or more, boundary-plane publication, a ragged row (partial last column)
+template <typename T, int KIND> using X3XhKernel = void (*)(StencilArgs<T>, ZPartBounds);
+template <typename T, int KIND, bool BIG, bool PUB> static X3XhKernel<T, KIND> x3_xh_kernel_ptr(bool rag) {
+  return rag ? stencil7x3_xh_kernel<T, KIND, BIG, PUB, true> : stencil7x3_xh_kernel<T, KIND, BIG, PUB, false>;
+}
+template <typename T, int KIND> static X3XhKernel<T, KIND> x3_xh_kernel_ptr(bool big, bool pub, bool rag) {
+  return big ? (pub ? x3_xh_kernel_ptr<T, KIND, true, true>(rag) : x3_xh_kernel_ptr<T, KIND, true, false>(rag))
+             : (pub ? x3_xh_kernel_ptr<T, KIND, false, true>(rag) : x3_xh_kernel_ptr<T, KIND, false, false>(rag));
+}
 
 // ---------------------------------------------------------------------------------------------------------
 static int64_t x3_resident_blocks(const void *kernel, int threads) {
@@ -883,8 +962,11 @@ bool stencil7x3_supported(const LocalDomain &dom, int64_t qi, const Rect3 &regio
     // whole periodic rows: x wraps in-kernel by DPP rotates (fp32, exactly 512 cells)
     if (!f32 || n.x != 512 || !(stencil7x2_wrappable_axes(dom, qi, 1) & 1)) return false;
   } else {
-    // x from 3-deep halos, in columns of CW cells
-    if (rad.x(-1) < 3 || rad.x(1) < 3 || n.x % x3_column_cells(es) != 0) return false;
+    // x from 3-deep halos, in columns of CW cells; a ragged row's last column holds r = n.x mod CW cells and reads
+    // the 3 halo cells beyond them inside its own chunks, so r <= CW - 3 (r = CW - 2, CW - 1 would need the right
+    // edge wave's machinery at the ragged end: such rows keep the fused pairs)
+    const int64_t cw = x3_column_cells(es);
+    if (rad.x(-1) < 3 || rad.x(1) < 3 || n.x < 3 || n.x % cw > cw - 3) return false;
   }
   if (!(wrapm & 2) && (rad.y(-1) < 3 || rad.y(1) < 3)) return false;
   if (!(wrapm & 4) && (rad.z(-1) < 3 || rad.z(1) < 3)) return false;
@@ -1031,12 +1113,14 @@ static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, 
   a.sphchunk = tune.x3sphchunk ? 1 : 0;
   a.sphr = int(sph.radius);
   const int nx = a.hix - a.lox, ny = a.hiy - a.loy, nz = a.hiz - a.loz;
-  a.gx = XH ? int(nx / x3_column_cells(int64_t(sizeof(T)))) : 1;
+  // XH: columns of CW cells; a ragged row's last column holds xr < CW of them (the schedule treats it as a whole one)
+  const int cw = int(x3_column_cells(int64_t(sizeof(T))));
+  a.gx = XH ? (nx + cw - 1) / cw : 1;
+  a.xr = XH ? nx - (a.gx - 1) * cw : nx;
+  const bool rag = XH && a.xr < cw;
   a.gy = (ny + YO - 1) / YO;
   const bool big = dom.buffer_bytes(qi) >= (int64_t(1) << 32) - 4096;
-  const void *kern = XH ? (big ? (const void *)stencil7x3_xh_kernel<T, KIND, true, false>
-                               : (const void *)stencil7x3_xh_kernel<T, KIND, false, false>)
-                        : x3_wrap_kernel_ptr<T, KIND>();
+  const void *kern = XH ? (const void *)x3_xh_kernel_ptr<T, KIND>(big, false, rag) : x3_wrap_kernel_ptr<T, KIND>();
   const int64_t cols = int64_t(a.gx) * a.gy;
   const int64_t resident = x3_resident_blocks(kern, 64 * NW);
   // CUs left to the transport kernels running beside the sweep (pipelined triples: the gated exchange)
@@ -1083,8 +1167,7 @@ static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, 
   a.clk = reinterpret_cast<unsigned long long *>(tune.blockClock);
   STENCIL_REQUIRE(a.sink, "stencil7x3: no store sink on device " << dom.gpu() << " (stencil7x3_supported first)");
   if constexpr (XH || !std::is_same<T, float>::value) {
-    auto *k = a.pub ? (big ? stencil7x3_xh_kernel<T, KIND, true, true> : stencil7x3_xh_kernel<T, KIND, false, true>)
-                    : (big ? stencil7x3_xh_kernel<T, KIND, true, false> : stencil7x3_xh_kernel<T, KIND, false, false>);
+    const X3XhKernel<T, KIND> k = x3_xh_kernel_ptr<T, KIND>(big, a.pub != nullptr, rag);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64, NW), 0, stream, a, zb);
   } else {
     if (a.pub)

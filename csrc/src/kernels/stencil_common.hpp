@@ -82,6 +82,7 @@ template <typename T> struct StencilArgs {
   char *sink;
   int early; // stencil7x2 row / col2: publish the src and u1 rows right after the u1 update, not before the barrier
   unsigned long long *clk; // stencil7x3 measurement: per-block start / end wall clock (null: off)
+  int xr; // stencil7x3 XH: cells of the last column inside the row (a ragged row's partial column; else the column width)
 };
 
 // periodic image of raw coordinate c along axis ax (identity unless the axis wraps)

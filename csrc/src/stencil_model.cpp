@@ -143,7 +143,19 @@ void StencilModel::init() {
     }
     // fused triples where the whole-row kernel cannot wrap x (rows other than 512 fp32 cells: the 1024-wide cbrt
     // shape, fp64): read x from halos (the XH form) and leave the x self copies in the exchange, one per three steps,
-    // instead of falling back to pairs that wrap x
+    // instead of falling back to pairs that wrap x. The exception: ragged rows (a partial last column of the XH
+    // form's 512 fp32 / 256 fp64 cells, stencil7x3.hip) of a sub-domain that is periodic onto itself along every
+    // axis (one GPU, w == 7). There the pairs that wrap x in-kernel won on most shapes measured on one MI355X
+    // (Gcells/s, triples vs pairs, 3 interleaved repeats, profiles/ragged_triples/): 645x645x323 940-960 vs
+    // 1072-1078, 645x323x645 983-987 vs 1098-1138, 323x645x645 940-992 vs 1005-1020, 813x813x204 978-993 vs
+    // 1039-1053; triples won on 813x407x407 (1041-1047 vs 960-983) and 407x407x813 (1184-1211 vs 1126-1133). The dead lanes of the partial
+    // column (37 % of 645's two columns) and the x self copies cost more than the third fused step saves, so such a
+    // sub-domain keeps the pairs. Cut sub-domains (not measured; bench.py times whole-region triples against the
+    // overlapped pairs and picks) and ragged rows whose x comes from halos anyway (wrap_self off, x cut, rows the
+    // pairs cannot wrap) take the triples
+    auto partialColumn = [&](const LocalDomain &d, int64_t q) {
+      return w == 7 && d.size().x % (2 * 64 * (16 / d.elem_size(q))) != 0; // x3_column_cells
+    };
     if (cfg_.temporal >= 3 && (w & 1) && doms0[0].backend() == Backend::Device) {
       StencilTune tw = cfg_.tune, th = cfg_.tune;
       tw.wrap = w;
@@ -152,7 +164,7 @@ void StencilModel::init() {
       for (const auto &d : doms0)
         for (int64_t q = 0; q < d.num_data(); ++q) {
           withWrap = withWrap && stencil7x3_supported(d, q, d.get_compute_region(), tw);
-          withHalo = withHalo && stencil7x3_supported(d, q, d.get_compute_region(), th);
+          withHalo = withHalo && stencil7x3_supported(d, q, d.get_compute_region(), th) && !partialColumn(d, q);
         }
       if (!withWrap && withHalo) w &= ~1;
     }
@@ -186,11 +198,16 @@ void StencilModel::init() {
   if (overlapToggle_ && doms0.size() == 1 && doms0[0].backend() == Backend::Device) {
     const auto li = dd_->get_local_interior(2);
     const Rect3 c = doms0[0].get_compute_region();
-    bool ok = li[0].lo.x == c.lo.x && li[0].hi.x == c.hi.x && li[0].lo.y == c.lo.y && li[0].hi.y == c.hi.y &&
-              dd_->gated_send_supported(pairTune_.wrap) && c.extent().z >= 4 * pubDepth_;
+    const bool geom = li[0].lo.x == c.lo.x && li[0].hi.x == c.hi.x && li[0].lo.y == c.lo.y && li[0].hi.y == c.hi.y &&
+                      c.extent().z >= 4 * pubDepth_;
+    bool ok = geom && dd_->gated_send_supported(pairTune_.wrap);
     for (int64_t q = 0; q < doms0[0].num_data() && ok; ++q) ok = stencil7x2_row_kernel_used(doms0[0], q, c, pairTune_);
-    if (ok) {
-      pipeOk_ = true;
+    pipeOk_ = ok;
+    // pipelined triples (mode 4) do not need the pairs' whole-row kernel, and their exchange may keep same-GPU
+    // translate copies (triples that read x from halos: ragged rows, 1024-cell rows, fp64): a gated exchange runs those
+    // behind the whole sweep, its co-located sends and receives on the published planes
+    pipe3Ok_ = ok || (geom && cfg_.temporal >= 3 && dd_->gated_send_supported(pairTune_.wrap, true));
+    if (pipeOk_ || pipe3Ok_) {
       const Dim3 e = c.extent();
       pubCells_ = uint64_t(e.x) * uint64_t(e.y) * uint64_t(std::min<int64_t>(e.z, 2 * pubDepth_)) *
                   uint64_t(doms0[0].num_data());
@@ -198,7 +215,7 @@ void StencilModel::init() {
       HIP_CHECK(hipExtMallocWithFlags((void **)&pubCounter_, 256, hipDeviceMallocUncached));
       HIP_CHECK(hipMemset(pubCounter_, 0, 256));
       HIP_CHECK(hipDeviceSynchronize());
-      if (cfg_.overlapMode == 3 && overlap_) pipelined_ = true;
+      if (pipeOk_ && cfg_.overlapMode == 3 && overlap_) pipelined_ = true;
     }
   }
   // single steps: the self-periodic axes are read in-kernel at their periodic image and their same-GPU copies leave
@@ -262,7 +279,8 @@ void StencilModel::init() {
   // overlapped pairs with the slabs after the interior sweep (set_overlap_mode(2)) from the start
   slabsAfter_ = pairs_ && overlap_ && cfg_.overlapMode == 2;
   // fused triples: device sub-domains of whole 512-cell fp32 rows wrapped in-kernel, or of 512-cell fp32 / 256-cell
-  // fp64 columns whose x halos come from the exchange (stencil7x3_supported); each other axis wraps in-kernel (its
+  // fp64 columns whose x halos come from the exchange, the last column whole or holding at most 509 / 253 cells
+  // (stencil7x3_supported; rows ending 1 or 2 cells short of a column keep pairs); each other axis wraps in-kernel (its
   // self copies leave the exchange) or reads the 3-deep halos of a depth-3 exchange, one per three steps.
   // Whole regions only, so not beside an overlapped exchange (set_overlap switches between the two). The spheres at
   // least 3 cells from the periodic faces (the intermediate steps evaluate them at unwrapped halo coordinates)
@@ -514,14 +532,14 @@ void StencilModel::enqueue_step(int k) {
     // pipelined triples (mode 4): as the pipelined pairs, this sweep's exchange was gated on the previous sweep's
     // boundary planes and ran beside the rest of that sweep; the sweep waits for it, leaves x2reserve CUs to the
     // next gated exchange and publishes its own first / last 3 z planes early (fixed march directions)
-    const bool gate = gateOk && dd_->gated_send_supported(pairTune_.wrap);
+    const bool gate = gateOk && dd_->gated_send_supported(pairTune_.wrap, true);
     if (gate) dd_->set_send_gate(pubCounter_, pubTotal_);
     dd_->exchange_async(nullptr, pairTune_.wrap);
     dd_->wait_exchange(0, compute_[0]);
     StencilTune ti = pairTune_;
     ti.reserveCUs = cfg_.tune.x2reserve;
     const Rect3 c = doms[0].get_compute_region();
-    const bool pub = dd_->gated_send_supported(pairTune_.wrap);
+    const bool pub = dd_->gated_send_supported(pairTune_.wrap, true);
     if (pub) {
       ti.publish = pubCounter_;
       ti.publishDepth = pubDepth_;

@@ -24,3 +24,25 @@ def stencil7x2_apply(dd, di: int, q: int, region, kind=_C.StencilKind.Jacobi, sp
     span them). One read and one write of the field per two steps (csrc/src/kernels/stencil7x2.hip)."""
     native = getattr(dd, "native", dd)
     _C.stencil7x2_apply(native, di, q, region, kind, spheres, stream, tune if tune is not None else _C.StencilTune())
+
+
+def stencil7x3_supported(dd, di: int, q: int, tune=None) -> bool:
+    """True when the fused three-step kernel can sweep quantity q of local sub-domain di: a device fp32/fp64 quantity
+    in the aligned row layout with at least 3 x 3 x 16 cells, face radii >= 3 (edges and corners >= 1) on every axis
+    that `tune.wrap` does not read in-kernel, and an x extent the kernel's columns cover: with x wrapped in-kernel
+    (`tune.wrap & 1`) fp32 rows of exactly 512 cells; with x read from halos any row whose last column of 512 fp32 /
+    256 fp64 cells holds at most 509 / 253 cells (a whole column, or a partial one that leaves room for the 3 halo
+    cells; rows ending 1 or 2 cells short of a whole column keep the fused pairs)."""
+    return _C.stencil7x3_supported(getattr(dd, "native", dd), di, q, tune if tune is not None else _C.StencilTune())
+
+
+def stencil7x3_apply(dd, di: int, q: int, kind=_C.StencilKind.Jacobi, spheres: bool = True, stream: int = 0,
+                     tune=None) -> bool:
+    """next = S(S(S(curr))) on the whole compute region of local sub-domain di -- three fused 7-point steps (deeper
+    temporal blocking), bitwise equal to three single steps -- for quantity q. Returns False without launching
+    where `stencil7x3_supported` refuses. The halos of curr that must be valid (exchange() first): depth 3 on the
+    faces, and depth >= 1 on every edge and corner whose axes are all read from halos; the axes set in `tune.wrap`
+    are read periodically in-kernel instead and need no halo. One read and one write of the field per three steps;
+    only cells of the compute region are written (csrc/src/kernels/stencil7x3.hip)."""
+    native = getattr(dd, "native", dd)
+    return _C.stencil7x3_apply(native, di, q, kind, spheres, stream, tune if tune is not None else _C.StencilTune())

@@ -211,10 +211,11 @@ struct X2Schedule {
   int rounds = 1; // > 1: block b marches part b / cm of columns b % cm, b % cm + cm, ... (cm = blocks / parts) in
                   // step with the others; parts 1 = whole columns
 };
-inline X2Schedule x2_lockstep_schedule(int64_t slots, int64_t cols, int64_t nz) {
+// rounds = false: never rounds (a kernel without the round loop: quarters plus second segments, or no lockstep)
+inline X2Schedule x2_lockstep_schedule(int64_t slots, int64_t cols, int64_t nz, bool rounds = true) {
   X2Schedule r;
   if (slots < 4 || cols < 1) return r;
-  if (cols > slots) {
+  if (cols > slots && rounds) {
     // more row groups than blocks (fp64 1024^3 as 256-cell columns: 4 x 128 groups): rounds of whole columns, every
     // block on one column per round, y-adjacent columns side by side (quarters plus leftovers would run most
     // columns as balanced second segments)
@@ -230,7 +231,7 @@ inline X2Schedule x2_lockstep_schedule(int64_t slots, int64_t cols, int64_t nz) 
   if (cm < 1 || nz < 64 || nz / P < 16) return r;
   r.parts = int(P);
   r.blocks = P * cm;
-  if (P == 4 && cm < cols && cols % 2 == 0) {
+  if (rounds && P == 4 && cm < cols && cols % 2 == 0) {
     // quarters over slots / 4 row groups leave the rest to balanced second segments; two rounds of P2 parts over
     // half the row groups each keep every segment in lockstep when they fill 15 / 16 of the slots in both rounds
     // (813x813x204: 102 groups = 2 rounds x 51 groups x 5 parts on 255 blocks, 928-931 -> 970-971 Gcells/s; an odd
@@ -245,6 +246,37 @@ inline X2Schedule x2_lockstep_schedule(int64_t slots, int64_t cols, int64_t nz) 
   }
   return r;
 }
+
+// The launch schedule of a fused-triple sweep (stencil7x3), decided in one place for stencil7x3_apply, the planner
+// (stencil7x3_plan) and the tests: `cols` (row group, column) pairs of `nz` planes on `slots` resident blocks.
+//   seg 1: the balanced (column, plane) split over `blocks` blocks (parts 0);
+//   seg 2: `parts` lockstep z parts over blocks / parts row groups, the other groups as second segments (the host plan,
+//          x3_plan, may still refine parts and blocks);
+//   seg 3: `rounds` lockstep rounds of `parts` z parts over blocks / parts column groups each.
+// Rounds exist only in the XH kernel (columns with x halos): the whole-row form (xh = false) never gets them, and
+// neither form does while publishing boundary planes (the publishing pass order is written for two passes). Such
+// sweeps run what the schedule gives without its rounds branches: seg 2 with the leftover groups as second segments,
+// or seg 1 where no part count is admissible. Pure host code, no GPU.
+struct X3Schedule {
+  int seg = 1, parts = 0;
+  int64_t blocks = 0;
+  int rounds = 1;
+};
+X3Schedule stencil7x3_schedule(bool xh, int64_t cols, int64_t nz, int64_t slots, const StencilTune &tune,
+                               bool publishing);
+// What stencil7x3_apply would launch for this sub-domain, kind and tune (nothing is launched): the kernel form, the
+// schedule's inputs (slots: the occupancy query less tune.reserveCUs' share, as apply computes it) and the launch after
+// the host plan. supported = false (every other field default) where stencil7x3_supported refuses.
+struct X3LaunchInfo {
+  bool supported = false;
+  bool xh = false, ragged = false; // columns with x halos (else whole rows wrapped in-kernel); a partial last column
+  int64_t cols = 0, slots = 0;
+  int seg = 0, parts = 0;
+  int64_t blocks = 0;
+  int rounds = 0;
+};
+X3LaunchInfo stencil7x3_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind,
+                                    const Spheres &sph, const StencilTune &tune);
 
 // axes (mask as StencilTune::wrap) stencil7_apply can wrap in-kernel for this quantity's layout: with tune.wrap set
 // the single step reads the periodic image along those axes instead of the halo (the region must span them)

@@ -747,6 +747,38 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("size"), py::arg("jacobi"), py::arg("tune") = py::none(), py::arg("slots") = 256);
   m.def(
+      "stencil7x3_schedule",
+      [](bool xh, int64_t cols, int64_t nz, int64_t slots, py::object tune, bool publishing) {
+        const X3Schedule r = stencil7x3_schedule(xh, cols, nz, slots,
+                                                 tune.is_none() ? StencilTune() : tune.cast<StencilTune>(), publishing);
+        return py::make_tuple(r.seg, r.parts, r.blocks, r.rounds);
+      },
+      py::arg("xh"), py::arg("cols"), py::arg("nz"), py::arg("slots"), py::arg("tune") = py::none(),
+      py::arg("publishing") = false,
+      "launch schedule of a fused-triple sweep (no GPU): (seg, parts, blocks, rounds) for the XH form (xh, columns with "
+      "x halos) or the whole-row form over cols (row group, column) pairs of nz planes on `slots` resident blocks; seg "
+      "1 = balanced split, 2 = lockstep parts plus second segments, 3 = lockstep rounds (XH form, not publishing)");
+  m.def(
+      "stencil7x3_launch_info",
+      [](DistributedDomain &dd, size_t di, int64_t q, StencilKind kind, bool spheres, const StencilTune &tune) {
+        // what stencil7x3_apply would launch for the sub-domain's compute region (nothing is launched)
+        const Spheres s = spheres ? Spheres::jacobi(dd.get_compute_region()) : Spheres();
+        const LocalDomain &d = dd.domains().at(di);
+        const X3LaunchInfo r = stencil7x3_launch_info(d, q, d.get_compute_region(), kind, s, tune);
+        py::dict o;
+        o["supported"] = r.supported;
+        o["form"] = !r.supported ? "none" : (r.xh ? "xh" : "wrap");
+        o["ragged"] = r.ragged;
+        o["cols"] = r.cols;
+        o["slots"] = r.slots;
+        o["seg"] = r.seg;
+        o["parts"] = r.parts;
+        o["blocks"] = r.blocks;
+        o["rounds"] = r.rounds;
+        return o;
+      },
+      py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("kind"), py::arg("spheres"), py::arg("tune"));
+  m.def(
       "x2_lockstep_schedule",
       [](int64_t slots, int64_t cols, int64_t nz) {
         const X2Schedule r = x2_lockstep_schedule(slots, cols, nz);

@@ -991,9 +991,15 @@ bool stencil7x3_supported(const LocalDomain &dom, int64_t qi, const Rect3 &regio
          (dom.pitch(qi).x * es) % 16 == 0;
 }
 
-// the lockstep schedule of a triple sweep over cols row groups (columns) of nz planes with `slots` resident blocks
-static X2Schedule x3_schedule(int64_t cols, int64_t nz, int64_t slots, const StencilTune &tune) {
-  X2Schedule ls = x2_lockstep_schedule(slots, cols, nz);
+// the launch schedule of a triple sweep over cols row groups (columns) of nz planes with `slots` resident blocks
+// (stencil_ops.hpp): the one decision stencil7x3_apply, stencil7x3_launch_info and stencil7x3_plan share
+X3Schedule stencil7x3_schedule(bool xh, int64_t cols, int64_t nz, int64_t slots, const StencilTune &tune,
+                               bool publishing) {
+  // rounds (seg 3) need the round loop, which only stencil7x3_xh_kernel has (stencil7x3_wrap_kernel runs two passes
+  // over the segments, and a round schedule gives it none: it would write nothing), and that loop's pass order while
+  // publishing is the two-pass one
+  const bool rounds = xh && !publishing;
+  X2Schedule ls = x2_lockstep_schedule(slots, cols, nz, rounds);
   if (tune.x3sched == 1) {
     // lockstep over as many row groups as possible: P parts of cm = min(cols, slots / P) columns, the leftover columns
     // as second segments; P minimises the steps of one block (each segment runs 4 warm-up steps). A first guess:
@@ -1014,7 +1020,7 @@ static X2Schedule x3_schedule(int64_t cols, int64_t nz, int64_t slots, const Ste
       }
     }
   }
-  if (tune.x3sched == 1 && cols > slots && !tune.publish) {
+  if (tune.x3sched == 1 && cols > slots && rounds) {
     // more row groups than resident blocks (fp64 1024^3 as 4 x 171 groups of 256-cell columns): rounds R of P z
     // parts over cm = ceil(cols / R) groups, every block in step with its y-neighbours in every round; leftover
     // groups as unsynchronised second segments re-fetch their halo rows (fp64 1024^3: 5.1 ms per triple and
@@ -1034,7 +1040,16 @@ static X2Schedule x3_schedule(int64_t cols, int64_t nz, int64_t slots, const Ste
         }
       }
   }
-  return ls;
+  X3Schedule r;
+  if (tune.x2lockstep && ls.parts > 0) {
+    r.seg = ls.rounds > 1 ? 3 : 2;
+    r.parts = ls.parts;
+    r.blocks = ls.blocks;
+    r.rounds = ls.rounds;
+  } else {
+    r.blocks = std::max<int64_t>(1, std::min<int64_t>(slots, cols * nz / 24));
+  }
+  return r;
 }
 
 struct X3Plan {
@@ -1097,11 +1112,22 @@ static X3Plan x3_plan(const StencilArgs<T> &a, bool jac, int64_t cols, int64_t s
   return pl;
 }
 
+// a triple sweep ready to launch: the kernel's arguments, the host plan's tables, the grid and what decided them
+template <typename T> struct X3Launch {
+  StencilArgs<T> a;
+  ZPartBounds zb;
+  uint32_t blocks;
+  bool big, rag;
+  int64_t cols, slots;
+};
+// everything stencil7x3_apply decides before the launch (stencil7x3_launch_info reports it without launching)
 template <typename T, int KIND, bool XH>
-static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph, hipStream_t stream,
-                       const StencilTune &tune) {
+static X3Launch<T> x3_prepare(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph,
+                              const StencilTune &tune) {
   constexpr int NW = 12, YO = NW - 6;
-  StencilArgs<T> a = make_args<T>(dom, qi, region, KIND == 0 ? StencilKind::Jacobi : StencilKind::Astaroth, sph);
+  X3Launch<T> L{};
+  StencilArgs<T> &a = L.a;
+  a = make_args<T>(dom, qi, region, KIND == 0 ? StencilKind::Jacobi : StencilKind::Astaroth, sph);
   a.flip = tune.alternateZ ? (dom.parity() & 1) : 0;
   a.nt = tune.nontemporal ? 1 : 0;
   a.wrapm = tune.wrap & 7;
@@ -1134,19 +1160,17 @@ static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, 
     a.pubHi = a.hiz - tune.publishDepth;
     a.flip = 0; // fixed march directions (x3_segments)
   }
-  a.seg = 1;
-  uint32_t blocks = uint32_t(std::max<int64_t>(1, std::min<int64_t>(slots, cols * nz / 24)));
-  const X2Schedule ls = x3_schedule(cols, nz, slots, tune);
-  if (tune.x2lockstep && ls.parts > 0) {
-    a.seg = ls.rounds > 1 ? 3 : 2;
+  const X3Schedule ls = stencil7x3_schedule(XH, cols, nz, slots, tune, tune.publish != nullptr);
+  a.seg = ls.seg;
+  uint32_t blocks = uint32_t(ls.blocks);
+  if (ls.seg != 1) {
     a.zparts = ls.parts;
     a.zrounds = ls.rounds;
-    blocks = uint32_t(ls.blocks);
   }
   // Lockstep parts (seg 2): the z-part bounds (sphere-weighted for Jacobi), the leftover groups' second segments
   // (StencilTune::x3left) and, with the cost model's P, the number of parts are planned per shape on the host
   // (x3_plan) and cached (host work of a few ms would otherwise precede every un-captured launch)
-  ZPartBounds zb{};
+  ZPartBounds &zb = L.zb;
   if (a.seg == 2) {
     static std::map<std::vector<int64_t>, X3Plan> cache;
     static std::mutex mu;
@@ -1162,12 +1186,28 @@ static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, 
     blocks = it->second.blocks;
     zb = it->second.b;
   }
-  dom.set_device();
   a.sink = x3_sink(dom.gpu(), false);
   a.clk = reinterpret_cast<unsigned long long *>(tune.blockClock);
+  L.blocks = blocks;
+  L.big = big;
+  L.rag = rag;
+  L.cols = cols;
+  L.slots = slots;
+  return L;
+}
+
+template <typename T, int KIND, bool XH>
+static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph, hipStream_t stream,
+                       const StencilTune &tune) {
+  constexpr int NW = 12;
+  const X3Launch<T> L = x3_prepare<T, KIND, XH>(dom, qi, region, sph, tune);
+  const StencilArgs<T> &a = L.a;
+  const ZPartBounds &zb = L.zb;
+  const uint32_t blocks = L.blocks;
+  dom.set_device();
   STENCIL_REQUIRE(a.sink, "stencil7x3: no store sink on device " << dom.gpu() << " (stencil7x3_supported first)");
   if constexpr (XH || !std::is_same<T, float>::value) {
-    const X3XhKernel<T, KIND> k = x3_xh_kernel_ptr<T, KIND>(big, a.pub != nullptr, rag);
+    const X3XhKernel<T, KIND> k = x3_xh_kernel_ptr<T, KIND>(L.big, a.pub != nullptr, L.rag);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64, NW), 0, stream, a, zb);
   } else {
     if (a.pub)
@@ -1199,11 +1239,12 @@ X3PlanInfo stencil7x3_plan(const Dim3 &size, bool jacobi, const StencilTune &tun
   const int64_t cols = a.gy, nz = size.z;
   X3PlanInfo r;
   r.groups = int(cols);
-  const X2Schedule ls = x3_schedule(cols, nz, slots, tune);
+  // the whole-row form, as apply decides it (never rounds)
+  const X3Schedule ls = stencil7x3_schedule(false, cols, nz, slots, tune, tune.publish != nullptr);
   r.parts = ls.parts;
-  r.blocks = int(ls.blocks);
+  r.blocks = ls.seg == 1 ? 0 : int(ls.blocks);
   r.rounds = ls.rounds;
-  if (!tune.x2lockstep || ls.parts <= 0 || ls.rounds > 1) return r;
+  if (ls.seg != 2) return r;
   a.zparts = ls.parts;
   const X3Plan pl = x3_plan(a, jacobi, cols, slots, uint32_t(ls.blocks), tune);
   r.parts = pl.P;
@@ -1238,6 +1279,37 @@ bool stencil7x3_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, S
         : apply_x3_t<float, 1, false>(dom, qi, region, sph, stream, tune);
   }
   return true;
+}
+
+template <typename T, int KIND, bool XH>
+static X3LaunchInfo x3_launch_info_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph,
+                                     const StencilTune &tune) {
+  const X3Launch<T> L = x3_prepare<T, KIND, XH>(dom, qi, region, sph, tune);
+  X3LaunchInfo r;
+  r.supported = true;
+  r.xh = XH;
+  r.ragged = L.rag;
+  r.cols = L.cols;
+  r.slots = L.slots;
+  r.seg = L.a.seg;
+  r.parts = L.a.seg == 1 ? 0 : L.a.zparts;
+  r.blocks = int64_t(L.blocks);
+  r.rounds = L.a.seg == 3 ? L.a.zrounds : 1;
+  return r;
+}
+
+X3LaunchInfo stencil7x3_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind,
+                                    const Spheres &sph, const StencilTune &tune) {
+  if (!stencil7x3_supported(dom, qi, region, tune)) return X3LaunchInfo();
+  const bool jac = kind == StencilKind::Jacobi, xh = !(tune.wrap & 1);
+  if (dom.elem_size(qi) == 8)
+    return jac ? x3_launch_info_t<double, 0, true>(dom, qi, region, sph, tune)
+               : x3_launch_info_t<double, 1, true>(dom, qi, region, sph, tune);
+  if (xh)
+    return jac ? x3_launch_info_t<float, 0, true>(dom, qi, region, sph, tune)
+               : x3_launch_info_t<float, 1, true>(dom, qi, region, sph, tune);
+  return jac ? x3_launch_info_t<float, 0, false>(dom, qi, region, sph, tune)
+             : x3_launch_info_t<float, 1, false>(dom, qi, region, sph, tune);
 }
 
 } // namespace stencil

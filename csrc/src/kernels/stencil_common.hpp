@@ -54,7 +54,7 @@ template <typename T> struct StencilArgs {
   int seg;                          // stencil7x2: 1 = balanced (column, plane) segments over gridDim.x blocks, 2 = lockstep
                                     // z parts, 3 = lockstep rounds of whole columns
   int zparts;                       // stencil7x2 lockstep: z parts per column (4 = quarters)
-  int zrounds;                      // stencil7x2 lockstep rounds (seg 3)
+  int zrounds;                      // lockstep rounds (seg 3): stencil7x2, and stencil7x3's XH form only
   int xfast;                        // stencil7x2: 1 = column index x-major (x-adjacent columns on one XCD)
   int remap;                        // stencil7x2: 1 = XCD-aware block remap
   // spheres, raw coordinates

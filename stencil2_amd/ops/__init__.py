@@ -11,5 +11,6 @@ from .kernels import (  # noqa: F401
     stencil7x2_apply,
     stencil7x2_supported,
     stencil7x3_apply,
+    stencil7x3_launch_info,
     stencil7x3_supported,
 )

@@ -36,6 +36,17 @@ def stencil7x3_supported(dd, di: int, q: int, tune=None) -> bool:
     return _C.stencil7x3_supported(getattr(dd, "native", dd), di, q, tune if tune is not None else _C.StencilTune())
 
 
+def stencil7x3_launch_info(dd, di: int, q: int, kind=_C.StencilKind.Jacobi, spheres: bool = True, tune=None) -> dict:
+    """What `stencil7x3_apply` would launch for quantity q of local sub-domain di with this kind, spheres and tune
+    (nothing is launched): `supported`, `form` ("wrap": whole rows wrapped in-kernel, "xh": columns with x halos),
+    `ragged` (a partial last column), `cols` ((row group, column) pairs), `slots` (resident blocks: the occupancy query
+    less the share of `tune.reserveCUs`), and the schedule `seg` (1 balanced split, 2 lockstep parts plus second
+    segments, 3 lockstep rounds), `parts`, `blocks`, `rounds`. The schedule is `_C.stencil7x3_schedule`'s, refined by
+    the host plan for seg 2."""
+    native = getattr(dd, "native", dd)
+    return _C.stencil7x3_launch_info(native, di, q, kind, spheres, tune if tune is not None else _C.StencilTune())
+
+
 def stencil7x3_apply(dd, di: int, q: int, kind=_C.StencilKind.Jacobi, spheres: bool = True, stream: int = 0,
                      tune=None) -> bool:
     """next = S(S(S(curr))) on the whole compute region of local sub-domain di -- three fused 7-point steps (deeper

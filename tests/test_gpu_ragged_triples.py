@@ -100,10 +100,19 @@ def test_ragged_triples_model(st, kind, size, fp64, gpus, cost, scale):
 
 def test_ragged_triples_more_row_groups_than_blocks(st):
     """More (row group, column) pairs than resident blocks (the schedule's rounds of whole column groups): the ragged
-    1029-cell row and the whole-column control of 1024 cells."""
-    for size in ((1024, 700, 16), (1029, 700, 16)):
+    1029-cell row (3 x 117 = 351 columns) and the whole-column control of 1024 cells (2 x 129 = 258 columns: with 700
+    rows it would have 234, fewer than the 256 resident blocks, and run the balanced split). Both are asserted to
+    launch rounds (ops.stencil7x3_launch_info)."""
+    from stencil2_amd.ops import stencil7x3_launch_info
+    for size, cols in (((1024, 771, 16), 258), ((1029, 700, 16), 351)):
         m, ref, nq = _model(st, "astaroth", size, quantities=1, wrap_self=False)
         assert m.temporal_triples() and m.wrap_axes() == 0, f"{size}: triples {m.temporal_triples()}"
+        t = st.StencilTune()
+        t.wrap = 0
+        info = stencil7x3_launch_info(m.domain, 0, 0, st.StencilKind.Astaroth, spheres=False, tune=t)
+        assert info["form"] == "xh" and info["ragged"] == (size[0] % 512 != 0) and info["cols"] == cols, info
+        assert info["cols"] > info["slots"] and info["seg"] == 3 and info["rounds"] > 1, f"{size}: no rounds: {info}"
+        assert info["blocks"] // info["parts"] * info["rounds"] >= cols and info["blocks"] <= info["slots"], info
         u = _field(size, False, 7)
         _set_field(m, u, nq)
         _run_and_compare(m, ref, nq, u, (3, 7, 2, 20, 1))

@@ -17,25 +17,30 @@ def _tune(**kw):
 
 
 SHAPES = [(512, 512, 512), (512, 510, 512), (512, 300, 256), (512, 1024, 512), (512, 96, 64), (1024, 512, 128),
-          (512, 200, 1000)]
+          (512, 200, 1000),
+          # more row groups than the 256 resident blocks (257 and 352), and 102 groups that two rounds of 5 parts would
+          # fill (x3sched 0): the whole-row kernel has no rounds, so these are lockstep parts plus leftover groups
+          (512, 1539, 16), (512, 2112, 16), (512, 1539, 112), (512, 610, 80)]
 
 
-@pytest.mark.parametrize("size", SHAPES)
-@pytest.mark.parametrize("jacobi", [True, False])
-@pytest.mark.parametrize("left", [0, 1, 2, 3])
-def test_leftover_tables_cover_every_plane_once(size, jacobi, left):
-    p = _C.stencil7x3_plan(size, jacobi, _tune(x3left=left))
-    if p.rounds > 1 or p.parts == 0:
+def _check_plan(p, size, left, slots=256):
+    """A whole-row plan: never rounds; lockstep parts (if any) within the slots; sphere-weighted bounds ordered; the
+    leftover groups' planes covered exactly once by the tables. Untabled leftovers (equal slices in the kernel) only
+    where the tables cannot hold them: more blocks than kLeftMaxBlocks = 256, or more than 65535 leftover planes."""
+    assert p.rounds == 1
+    if p.parts == 0:  # balanced split (no admissible part count: fewer than 16 planes per part)
+        assert p.blocks == 0 and not p.tabled
         return
     nz = size[2]
-    assert p.parts * p.lockstep_groups == p.blocks and p.lockstep_groups <= p.groups
+    assert p.parts * p.lockstep_groups == p.blocks <= slots and p.lockstep_groups <= p.groups
+    assert nz // p.parts >= 16
     if p.zb:  # sphere-weighted parts: parts - 1 nondecreasing bounds inside [0, nz] per group
         for g in range(len(p.zb) // (p.parts - 1)):
             b = p.zb[g * (p.parts - 1):(g + 1) * (p.parts - 1)]
             assert all(0 <= x <= nz for x in b) and b == sorted(b)
     G = p.groups - p.lockstep_groups
     if not p.tabled:
-        assert left == 0 or G == 0 or G * nz > 65535
+        assert left == 0 or G == 0 or G * nz > 65535 or p.blocks > 256
         return
     assert left != 0 and len(p.l0) == len(p.l1) == len(p.odd) == p.blocks
     cover = collections.Counter()
@@ -43,6 +48,22 @@ def test_leftover_tables_cover_every_plane_once(size, jacobi, left):
         assert 0 <= a <= b <= G * nz
         cover.update(range(a, b))
     assert len(cover) == G * nz and set(cover.values()) == {1}
+
+
+@pytest.mark.parametrize("size", SHAPES)
+@pytest.mark.parametrize("jacobi", [True, False])
+@pytest.mark.parametrize("left", [0, 1, 2, 3])
+def test_leftover_tables_cover_every_plane_once(size, jacobi, left):
+    _check_plan(_C.stencil7x3_plan(size, jacobi, _tune(x3left=left)), size, left)
+
+
+@pytest.mark.parametrize("size", SHAPES)
+@pytest.mark.parametrize("jacobi", [True, False])
+@pytest.mark.parametrize("left", [0, 3])
+def test_leftover_tables_with_the_pairs_schedule(size, jacobi, left):
+    """x3sched 0 (the fused pairs' lockstep schedule): its rounds branches (more groups than slots; an even group count
+    in two rounds, (512, 610, 80)) are not for the whole-row kernel either."""
+    _check_plan(_C.stencil7x3_plan(size, jacobi, _tune(x3left=left, x3sched=0)), size, left)
 
 
 @pytest.mark.parametrize("size", [(512, 512, 512), (512, 420, 256), (512, 1024, 512)])
@@ -93,7 +114,8 @@ def test_random_shapes_and_knobs_keep_the_invariants():
                   x3sphw=rnd.choice([0.0, 0.3, 0.45, 0.6, 1.0]))
         slots = rnd.choice([256, 248, 128, 64, 300])
         p = _C.stencil7x3_plan(size, jac, t, slots)
-        if p.rounds > 1 or p.parts == 0:
+        assert p.rounds == 1, (size, slots)
+        if p.parts == 0:
             continue
         assert p.parts * p.lockstep_groups == p.blocks <= slots
         if p.tabled:
@@ -103,3 +125,42 @@ def test_random_shapes_and_knobs_keep_the_invariants():
                 assert 0 <= a <= b <= G * nz
                 cover.update(range(a, b))
             assert len(cover) == G * nz and set(cover.values()) == {1}
+
+
+def test_schedule_gives_rounds_only_to_the_xh_form_and_never_while_publishing():
+    """_C.stencil7x3_schedule, the one launch decision of stencil7x3_apply and stencil7x3_plan, over random columns,
+    depths, slots and knobs: the whole-row form (no round loop in its kernel) and a publishing sweep of either form
+    never get rounds; XH rounds visit every column with all their blocks resident and at least 16 planes per part;
+    lockstep launches never exceed the slots."""
+    import random
+    rnd = random.Random(7)
+    seen = collections.Counter()
+    for i in range(4000):
+        cols, nz = rnd.randint(1, 1200), rnd.randint(16, 1200)
+        if i % 4 == 0:  # the two-round branch of the pairs' schedule: an even group count filling 15 / 16 of the slots
+            cols = 2 * rnd.randint(20, 64)
+        slots = rnd.choice([64, 128, 248, 256, 300])
+        t = _tune(x3sched=rnd.choice([0, 1]), x3parts=rnd.choice([0, 0, 0, 2, 3, 4, 5, 8]))
+        for xh in (False, True):
+            for pub in (False, True):
+                seg, parts, blocks, rounds = _C.stencil7x3_schedule(xh, cols, nz, slots, t, pub)
+                what = (xh, cols, nz, slots, t.x3sched, t.x3parts, pub, seg, parts, blocks, rounds)
+                assert seg in (1, 2, 3) and (seg == 3) == (rounds > 1) and rounds >= 1, what
+                if not xh or pub:
+                    assert rounds == 1, what
+                if seg == 1:
+                    assert parts == 0 and 1 <= blocks <= slots, what
+                    continue
+                assert parts >= 1 and blocks % parts == 0 and blocks <= slots and nz // parts >= 16, what
+                cm = blocks // parts
+                assert 1 <= cm <= cols, what
+                if rounds > 1:
+                    assert cm * rounds >= cols, what
+                    # the same columns, depth and slots without rounds: what the whole-row form runs instead
+                    s2 = _C.stencil7x3_schedule(False, cols, nz, slots, t, pub)
+                    assert s2[3] == 1 and s2[0] in (1, 2), (what, s2)
+                seen[(xh, pub, t.x3sched, seg)] += 1
+    # every branch was drawn: rounds from both schedules, and parts / balanced splits for the whole-row form on both
+    for sched in (0, 1):
+        assert seen[(True, False, sched, 3)] > 50, seen
+        assert seen[(False, False, sched, 2)] > 50 and seen[(True, True, sched, 2)] > 50, seen

@@ -65,6 +65,9 @@ constexpr uint32_t kNarrowMaxUnits = 4;
 // rows of whole 64-B sectors (x faces widened to sectors): 4 consecutive lanes move one row, so every wave
 // instruction reads / writes 16 complete sectors instead of 64 partial ones
 constexpr uint32_t kSegWide = 1;
+// The planner's narrow-row rule: true when the items of `s` are whole rows (the kernel's row-width instances 1..4),
+// false when they are single vector units. The work table and the shape query of the tests both ask this function.
+inline bool copy_seg_row_items(const CopySeg &s) { return s.row_units <= kNarrowMaxUnits && !(s.flags & kSegWide); }
 struct CopyWork {
   uint32_t seg;
   uint32_t first;

@@ -299,6 +299,30 @@ PYBIND11_MODULE(_C, m) {
       py::arg("seconds"), py::arg("stream") = 0);
   m.def("set_copy_block_items", &set_copy_block_items, py::arg("narrow"), py::arg("wide"));
   m.def("set_copy_small_rows", &set_copy_small_rows, py::arg("max_items"), py::arg("per_entry"));
+  // the shape make_copy_seg gives one box copy and the planner's item rule for it (host only, nothing is launched):
+  // which (vector width, row width) instance of the copy kernel the copy runs
+  m.def(
+      "copy_seg_shape",
+      [](uintptr_t src, int64_t srcY, int64_t srcZ, uintptr_t dst, int64_t dstY, int64_t dstZ, const Dim3 &ext,
+         int64_t elemSize) {
+        StridedBox s, d;
+        s.base = reinterpret_cast<char *>(src);
+        s.ystride = srcY;
+        s.zstride = srcZ;
+        d.base = reinterpret_cast<char *>(dst);
+        d.ystride = dstY;
+        d.zstride = dstZ;
+        const CopySeg sg = make_copy_seg(s, d, ext, elemSize);
+        py::dict r;
+        r["vec"] = sg.vec;
+        r["row_units"] = sg.row_units;
+        r["ny"] = sg.ny;
+        r["units"] = sg.units;
+        r["rows"] = copy_seg_row_items(sg);
+        return r;
+      },
+      py::arg("src_ptr"), py::arg("src_ystride"), py::arg("src_zstride"), py::arg("dst_ptr"), py::arg("dst_ystride"),
+      py::arg("dst_zstride"), py::arg("ext"), py::arg("elem_size"));
   m.def("ipc_event_stress", &ipc_event_stress, py::arg("group"), py::arg("device"), py::arg("n"), py::arg("after"),
         py::call_guard<py::gil_scoped_release>());
   m.def(
@@ -593,6 +617,7 @@ PYBIND11_MODULE(_C, m) {
       .def("set_partition_objective", &DistributedDomain::set_partition_objective)
       .def("partition_objective", &DistributedDomain::partition_objective)
       .def("set_comm_max_blocks", &DistributedDomain::set_comm_max_blocks)
+      .def("set_translate_max_blocks", &DistributedDomain::set_translate_max_blocks)
       .def("set_gpus", &DistributedDomain::set_gpus)
       .def("gpus", &DistributedDomain::gpus)
       .def("set_backend", &DistributedDomain::set_backend)

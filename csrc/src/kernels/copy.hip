@@ -210,7 +210,7 @@ static std::vector<CopySeg> pair_narrow_segs(const std::vector<CopySeg> &in) {
   std::vector<CopySeg> out;
   std::vector<bool> used(in.size(), false);
   auto narrow = [](const CopySeg &s) {
-    return s.units && s.row_units <= kNarrowMaxUnits && !s.src2 && !(s.flags & kSegWide);
+    return s.units && copy_seg_row_items(s) && !s.src2;
   };
   auto compatible = [&](const CopySeg &a, const CopySeg &b) {
     return narrow(b) && b.vec == a.vec && b.row_units == a.row_units && b.ny == a.ny && b.units == a.units &&
@@ -272,7 +272,7 @@ static std::vector<CopyWork> work_table(const std::vector<CopySeg> &segs, uint32
   for (uint32_t si = 0; si < segs.size(); ++si) {
     const CopySeg &s = segs[si];
     if (!s.units) continue;
-    const bool rows = s.row_units <= kNarrowMaxUnits && !(s.flags & kSegWide);
+    const bool rows = copy_seg_row_items(s);
     const uint64_t items = rows ? s.units / s.row_units : s.units;
     STENCIL_REQUIRE(items < (1ull << 32), "copy segment too large");
     // small row segments (edges: a few hundred scattered cells) are split finer, so their latency-bound items run

@@ -62,6 +62,35 @@ def scenario_exchange(backend, methods, radius_name, size):
     return bad
 
 
+def scenario_exchange_types(backend, methods, radius_name, size):
+    """Nine quantities of element sizes 1..24 B (named dtypes and opaque elements) against the byte oracle, 3 epochs
+    with swap(): across ranks every element size goes through the packed transports (on the device: the fused wait +
+    copy + signal kernel of the Colocated transport)."""
+    import copy_types_cases as cases
+    from stencil2_amd.utils.testing import check_exchange_bytes, fill_bytes_pattern
+    g = st.init_process_group()
+    radius = cases.radii(st)[radius_name]
+    dd = st.DistributedDomain(*size, group=g)
+    dd.set_backend(backend)
+    dd.set_transport_options(transport_from_env())
+    dd.set_radius(radius)
+    if backend == st.Backend.Device:
+        dd.set_gpus([0])
+    dd.set_methods(methods)
+    qs = cases.add_mixed(dd)
+    dd.realize()
+    bad = 0
+    for it in range(3):
+        for q in qs:
+            fill_bytes_pattern(dd, q, it)
+        print(f"rank {g.rank()} epoch {it} exchange", flush=True)
+        dd.exchange()
+        bad += sum(check_exchange_bytes(dd, q, radius, it) for q in qs)
+        dd.swap()
+    print(f"rank {g.rank()} types bad {bad} plan {[str(e.method) for e in dd.plan()][:3]}")
+    return bad
+
+
 def scenario_canary(backend, methods, radius_name, size, iters=12):
     """Race canary: every iteration writes iteration-tagged interiors, poisons every halo with NaN
     (float) / -1 (int), then exchanges back to back with no barrier between ranks. A halo from another iteration
@@ -375,6 +404,8 @@ def main():
         methods = methods | getattr(st.MethodFlags, name)
     if sc == "exchange":
         bad = scenario_exchange(backend, methods, sys.argv[2], tuple(int(v) for v in sys.argv[3].split(",")))
+    elif sc == "exchange_types":
+        bad = scenario_exchange_types(backend, methods, sys.argv[2], tuple(int(v) for v in sys.argv[3].split(",")))
     elif sc == "canary":
         bad = scenario_canary(backend, methods, sys.argv[2], tuple(int(v) for v in sys.argv[3].split(",")))
     elif sc == "selftest":

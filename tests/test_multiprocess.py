@@ -20,6 +20,14 @@ def test_staged_exchange_ranks(n, radius, size):
     _ok(run_ranks(n, WORKER, ["exchange", radius, size]))
 
 
+@pytest.mark.parametrize("n,radius,size", [(2, "fec", "20,12,10"), (3, "asym", "20,12,10"), (3, "fec", "15,9,8")])
+def test_staged_exchange_mixed_types_ranks(n, radius, size):
+    """nine quantities of element sizes 1..24 B (opaque 3, 6, 12 and 24 B among them) staged over TCP, byte oracle"""
+    outs = run_ranks(n, WORKER, ["exchange_types", radius, size])
+    _ok(outs)
+    assert all("types bad 0" in out for _, out in outs)
+
+
 def test_fake_two_nodes_nodeaware():
     outs = run_ranks(4, WORKER, ["exchange", "r1", "16,12,10"],
                      per_rank_env=lambda r: {"STENCIL_HOSTNAME": f"node{r // 2}"})

@@ -58,7 +58,7 @@ int main(int argc, char **argv) {
   ArgParser p("7-point stencil kernel sweep on one GPU");
   p.option(&n, "--n", "cube edge").option(&iters, "--iters", "timed launches per config")
       .option(&reps, "--reps", "repetitions of the whole sweep (interleaved)")
-      .option(&only, "--only", "run only 'lds', 'reg' or 'copy'");
+      .option(&only, "--only", "run only 'lds', 'reg', 'copy' or 'star' (weighted stars of radius 1-3 beside stencil7)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -330,6 +330,51 @@ int main(int argc, char **argv) {
     free_copy_plan(up);
     HIP_CHECK(hipHostFree(hostBuf));
     HIP_CHECK(hipFree(devBuf));
+  }
+  if (only == "star" || only == "starzc") {
+    // weighted stars of radius 1, 2, 3 (fp32) on a depth-3 domain, interleaved per repetition with the default
+    // 7-point single step (variant 2) on the radius-1 domain: both read the field once and write it once
+    LocalDomain l3(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
+    l3.set_radius(Radius::face_edge_corner(3, 0, 0));
+    l3.add_data<float>("d");
+    l3.realize();
+    jacobi_init(l3, 0, l3.get_full_region(), s);
+    s.sync();
+    const Rect3 reg3 = l3.get_compute_region();
+    for (int rep = 0; rep < reps && only == "starzc"; ++rep)
+      for (int r = 1; r <= 3; ++r) // the z-chunk length (blocks per launch) around the automatic choice
+        for (int zc : {0, 32, 43, 52, 64, 86, 128}) {
+          StencilTune t;
+          t.zchunk = zc;
+          StarWeights w;
+          w.radius = r;
+          w.center = 0.25;
+          for (int ax = 0; ax < 3; ++ax)
+            for (int sd = 0; sd < 2; ++sd)
+              for (int k = 0; k < r; ++k) w.w[ax][sd][k] = 0.125 / r;
+          const StarLaunchInfo li = stencil_star_launch_info(l3, 0, reg3, w, t);
+          const double us = timeit([&] { stencil_star_apply(l3, 0, reg3, w, s, t); });
+          std::printf("stencil_star,%d,2,%d,%.2f,%.1f,%.3f,blocks%lld\n", r, li.zchunk, us, cells / us / 1e3,
+                      cells * 8 / us / 1e6, (long long)li.blocks);
+        }
+    for (int rep = 0; rep < reps && only == "star"; ++rep) {
+      StencilTune t;
+      const double us7 = timeit([&] { stencil7_apply(ld, 0, reg, StencilKind::Jacobi, sph, s, t); });
+      std::printf("stencil7,%d,%d,%d,%.2f,%.1f,%.3f,nw%d\n", t.variant, t.ty, t.zchunk, us7, cells / us7 / 1e3,
+                  cells * 8 / us7 / 1e6, t.nw);
+      for (int r = 1; r <= 3; ++r) {
+        StarWeights w; // identity + a sixth of the 2nd-order Laplacian spread over the radius (values do not matter)
+        w.radius = r;
+        w.center = 0.25;
+        for (int ax = 0; ax < 3; ++ax)
+          for (int sd = 0; sd < 2; ++sd)
+            for (int k = 0; k < r; ++k) w.w[ax][sd][k] = 0.125 / r;
+        const StarLaunchInfo li = stencil_star_launch_info(l3, 0, reg3, w, t);
+        const double us = timeit([&] { stencil_star_apply(l3, 0, reg3, w, s, t); });
+        std::printf("stencil_star,%d,2,%d,%.2f,%.1f,%.3f,path%d\n", r, li.zchunk, us, cells / us / 1e3,
+                    cells * 8 / us / 1e6, li.path);
+      }
+    }
   }
   for (int rep = 0; rep < reps; ++rep)
   if (only == "x2pp") {

@@ -289,6 +289,38 @@ void stencil7_mfma_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region
 void stencil7_apply_regions(const LocalDomain &dom, int64_t qi, const std::vector<Rect3> &regions, StencilKind kind,
                             const Spheres &sph, hipStream_t stream, const StencilTune &tune = StencilTune());
 
+// Weighted star stencil of radius 1-3 (stencil_star.hip): for a quantity of element type T (fp32 / fp64)
+//   acc = center * u(c); for axis in x, y, z: for k in 1..radius: acc += w[axis][-][k] * u(c - k e); acc += w[axis][+][k] * u(c + k e)
+// with the weights converted to T once on the host and every product and sum its own IEEE rounding in T in exactly
+// this order (no FMA contraction; zero weights are multiplied like any other, so NaN / Inf propagate). All 6 radius + 1
+// weights are independent (upwind stars work). Bitwise equal to stencil2_amd.ops.star_step_reference.
+struct StarWeights {
+  int radius = 1;
+  double center = 0;
+  double w[3][2][3] = {}; // [axis x, y, z][0: -, 1: +][k - 1]
+};
+// an fp32 / fp64 quantity (or opaque 4- / 8-byte elements), radius 1..3 and all six face radii >= radius
+bool stencil_star_supported(const LocalDomain &dom, int64_t qi, const StarWeights &w);
+// next(region) = star(curr) for one quantity of one LocalDomain; only cells of `region` (global coordinates, inside
+// the compute region; empty: no-op) are written. Neighbours come from the halos of curr (exchange() first; edges and
+// corners are not read: Radius::face_edge_corner(radius, 0, 0) suffices). Device sub-domains in the aligned vector
+// layout (as stencil7_apply's) run a 2.5D z-march: one 16-B x chunk of 2 rows per lane, a register ring of the
+// 2 radius + 1 planes, the block's 16 rows plus `radius` halo rows each side shared through LDS, x neighbours from
+// adjacent lanes, each source cell read from HBM about once per sweep; any other layout runs one thread per cell,
+// Backend::Host a plain loop. Of `tune`: zchunk (0 = one round of resident blocks, at most two per CU, chunks of >= 16 planes),
+// nontemporal, xcdRemap, alternateZ; tune.wrap != 0 is refused (no in-kernel wrap, forwarding or temporal fusion).
+void stencil_star_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StarWeights &w,
+                        hipStream_t stream, const StencilTune &tune = StencilTune());
+// What stencil_star_apply would run for these arguments (nothing is launched; the same refusals raise)
+struct StarLaunchInfo {
+  int path = 0;       // -1 nothing (empty region), 0 host loop, 1 one thread per cell, 2 the z-march kernel
+  int zchunk = 0;     // z-march: planes per block
+  int zchunks = 0;    // z-march: chunks along z
+  int64_t blocks = 0; // z-march: blocks of the launch
+};
+StarLaunchInfo stencil_star_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StarWeights &w,
+                                        const StencilTune &tune = StencilTune());
+
 // Jacobi init: curr = 0.5 on `region` (reference bin/jacobi3d.cu:18-29)
 void jacobi_init(const LocalDomain &dom, int64_t qi, const Rect3 &region, hipStream_t stream);
 // Astaroth init: interior = sin(2*pi/period*(origin+x+y+z)) (x,y,z raw indices), halo = -10 (astaroth_sim.cu:14-61)

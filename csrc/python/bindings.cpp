@@ -753,6 +753,43 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("kind"), py::arg("spheres"),
         py::arg("stream"), py::arg("tune"), py::call_guard<py::gil_scoped_release>());
+  py::class_<StarWeights>(m, "StarWeights")
+      .def(py::init<>())
+      .def_readwrite("radius", &StarWeights::radius)
+      .def_readwrite("center", &StarWeights::center)
+      .def("get", [](const StarWeights &w, int axis, int side, int k) {
+        STENCIL_REQUIRE(axis >= 0 && axis < 3 && side >= 0 && side < 2 && k >= 1 && k <= 3, "StarWeights index");
+        return w.w[axis][side][k - 1];
+      }, py::arg("axis"), py::arg("side"), py::arg("k"), "weight of offset -k (side 0) / +k (side 1) along axis 0..2")
+      .def("set", [](StarWeights &w, int axis, int side, int k, double v) {
+        STENCIL_REQUIRE(axis >= 0 && axis < 3 && side >= 0 && side < 2 && k >= 1 && k <= 3, "StarWeights index");
+        w.w[axis][side][k - 1] = v;
+      }, py::arg("axis"), py::arg("side"), py::arg("k"), py::arg("value"));
+  m.def("stencil_star_supported",
+        [](DistributedDomain &dd, size_t di, int64_t q, const StarWeights &w) {
+          return stencil_star_supported(dd.domains().at(di), q, w);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("weights"));
+  m.def("stencil_star_apply",
+        [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &region, const StarWeights &w, uintptr_t stream,
+           const StencilTune &tune) {
+          stencil_star_apply(dd.domains().at(di), q, region, w, reinterpret_cast<hipStream_t>(stream), tune);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("stream"),
+        py::arg("tune"), py::call_guard<py::gil_scoped_release>());
+  m.def("stencil_star_launch_info",
+        [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &region, const StarWeights &w, const StencilTune &tune) {
+          // what stencil_star_apply would run (nothing is launched)
+          const StarLaunchInfo r = stencil_star_launch_info(dd.domains().at(di), q, region, w, tune);
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["zchunk"] = r.zchunk;
+          o["zchunks"] = r.zchunks;
+          o["blocks"] = r.blocks;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("tune"));
   py::class_<X3PlanInfo>(m, "X3PlanInfo")
       .def_readonly("parts", &X3PlanInfo::parts)
       .def_readonly("blocks", &X3PlanInfo::blocks)

@@ -5,12 +5,22 @@ from .reference import (  # noqa: F401
     jacobi_spheres,
     jacobi_step_reference,
     periodic_gather,
+    star_step_reference,
 )
 from .kernels import (  # noqa: F401
+    star_apply,
+    star_launch_info,
+    star_supported,
     stencil7_apply,
     stencil7x2_apply,
     stencil7x2_supported,
     stencil7x3_apply,
     stencil7x3_launch_info,
     stencil7x3_supported,
+)
+from .star import (  # noqa: F401
+    diffusion_star,
+    laplacian_star,
+    star_to_lists,
+    star_weights,
 )

@@ -57,3 +57,35 @@ def stencil7x3_apply(dd, di: int, q: int, kind=_C.StencilKind.Jacobi, spheres: b
     only cells of the compute region are written (csrc/src/kernels/stencil7x3.hip)."""
     native = getattr(dd, "native", dd)
     return _C.stencil7x3_apply(native, di, q, kind, spheres, stream, tune if tune is not None else _C.StencilTune())
+
+
+def _tune(tune):
+    return tune if tune is not None else _C.StencilTune()
+
+
+def star_supported(dd, di: int, q: int, weights) -> bool:
+    """True when `star_apply` can run `weights` on quantity q of local sub-domain di: an fp32 / fp64 quantity (or
+    opaque 4- / 8-byte elements), radius 1..3 and all six face radii of the domain >= that radius."""
+    return _C.stencil_star_supported(getattr(dd, "native", dd), di, q, weights)
+
+
+def star_apply(dd, di: int, q: int, weights, region=None, stream: int = 0, tune=None):
+    """next(region) = weighted star stencil of curr (`weights`: ops.star_weights / laplacian_star / diffusion_star)
+    for quantity q of local sub-domain di; `region` (global coordinates) defaults to the sub-domain's compute region
+    and only its cells are written. The face halos of curr must be valid to depth `weights.radius` (exchange() first).
+    Every product and sum is its own rounding in the quantity's type, in the order of `star_step_reference`, so the
+    result is bitwise equal to it (csrc/src/kernels/stencil_star.hip)."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    _C.stencil_star_apply(native, di, q, region, weights, stream, _tune(tune))
+
+
+def star_launch_info(dd, di: int, q: int, weights, region=None, tune=None) -> dict:
+    """What `star_apply` would run for these arguments (nothing is launched; the same refusals raise): `path` ("fast":
+    the z-march kernel of the aligned vector layout, "generic": one thread per cell, "host", "none": empty region) and
+    the z-march launch `zchunk` (planes per block), `zchunks`, `blocks`."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return _C.stencil_star_launch_info(native, di, q, region, weights, _tune(tune))

@@ -102,5 +102,23 @@ def astaroth_init_reference(size_xyz, radius: int, period: float, dtype=torch.fl
     return torch.sin(k * x + k * y + k * z).to(dtype)
 
 
+def star_step_reference(u: torch.Tensor, weights) -> torch.Tensor:
+    """One weighted star step (`weights`: _C.StarWeights, see ops.star) on a periodic global (z, y, x) grid: the
+    oracle of `star_apply`. acc = center * u, then per axis x, y, z and k = 1..radius: acc + w[-k] * u(c - k), then
+    acc + w[+k] * u(c + k). The weights are 0-dim tensors of u's dtype (one conversion from double) and every product
+    and every sum is a separate op, so each is rounded on its own in that dtype."""
+    def wt(v):
+        return torch.tensor(v, dtype=torch.float64).to(u.dtype).to(u.device)
+
+    acc = wt(weights.center) * u
+    for ax, dim in enumerate((2, 1, 0)):
+        for k in range(1, weights.radius + 1):
+            term = wt(weights.get(ax, 0, k)) * torch.roll(u, k, dim)  # u(c - k e)
+            acc = acc + term
+            term = wt(weights.get(ax, 1, k)) * torch.roll(u, -k, dim)  # u(c + k e)
+            acc = acc + term
+    return acc
+
+
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "math"]

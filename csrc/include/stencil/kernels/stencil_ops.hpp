@@ -8,6 +8,7 @@
 // (y-halo rows are shared through L1/L2 by the 4 waves of a block, x-neighbours come from adjacent lanes by
 // ds_bpermute). Blocks are remapped XCD-aware so y/z-adjacent tiles share an XCD's L2. Summation order and the
 // division by 6 are the reference's, so results are bitwise identical to a sequential fp32 evaluation.
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -246,6 +247,74 @@ inline X2Schedule x2_lockstep_schedule(int64_t slots, int64_t cols, int64_t nz, 
   }
   return r;
 }
+
+// The resident blocks a launch may fill when it leaves reserveCUs of the device's `cus` CUs (at most half of them) to
+// the kernels of another stream (the transports beside an overlapped sweep): the one slots formula of every kernel
+inline int64_t slots_less_reserved(int64_t resident, int reserveCUs, int cus) {
+  const int64_t perCU = std::max<int64_t>(1, resident / std::max(1, cus));
+  return std::max<int64_t>(perCU, resident - perCU * std::min(reserveCUs, cus / 2));
+}
+
+// The kernel form of a fused-pair sweep (stencil7x2), decided in one place for stencil7x2_apply, its launch report
+// (stencil7x2_launch_info), stencil7x2_row_kernel_used and stencil7x2_wrappable_axes. The row forms (fp32 only) run
+// one wave per whole periodic row with x wrapped in-kernel: Row = 512 cells, two chunks per lane; Ragged2 / Ragged3 =
+// 257-511 / 513-768 cells, 2 / 3 chunks per lane with the row-end cells broadcast for the wrap; Tail = 769-832 cells,
+// three chunks plus one tail cell per lane. Col2 = x a whole number of two-chunk columns (512 fp32 / 256 fp64 cells);
+// Column = the one-chunk column kernel, which takes everything else.
+enum class X2Form : int { Row = 0, Ragged2, Ragged3, Tail, Col2, Column };
+inline bool x2_row_form(X2Form f) { return f <= X2Form::Tail; }
+// the row widths some row form takes
+inline bool x2_row_width(int64_t nx) { return nx > 256 && nx <= 832; }
+// elemSize 4 / 8; nx = the region's x extent; x0 = its first x cell counted from the first interior cell of the row
+// (16-B aligned in memory: the forms other than Column need the region to start on a chunk); wrap, x2row as
+// StencilTune's; publishing = tune.publish set (only the row forms publish: any other form is reported as Column, and
+// apply refuses it); bufferBytes = LocalDomain::buffer_bytes (the row forms address the field by 32-bit buffer offsets).
+// Pure host code, no GPU.
+inline X2Form stencil7x2_form(int64_t elemSize, int64_t nx, int64_t x0, int wrap, int x2row, bool publishing,
+                              int64_t bufferBytes) {
+  if (!x2row) return X2Form::Column;
+  const int64_t V = 16 / elemSize, cw = 128 * V; // cells per chunk, per two-chunk column
+  const bool onChunk = x0 % V == 0;
+  if (elemSize == 4 && (wrap & 1) && onChunk && x2_row_width(nx) && bufferBytes < (int64_t(1) << 32) - 4096) {
+    // Ragged periodic rows: H = 2 / 3 chunks per lane (one plane of lookahead: the 3-chunk window leaves no registers
+    // for more). Four chunks per lane (rows of 769-1024) need 10-wave blocks for the LDS and spill at their 168-VGPR
+    // budget: 358 vs 668 Gcells/s for the column kernel at 813x407x407 (profiles/r2/r2_ragged_shapes.log); 8-wave
+    // blocks (2 waves per SIMD, 200 VGPRs, 4 output rows of 8) 597 vs 668 (r2_ragged_h4_8waves.log). Not instantiated:
+    // rows of 769-832 cells (the 4-GPU ladder's 813) run three chunks per lane plus one tail cell per lane.
+    return nx == 512 ? X2Form::Row : nx < 512 ? X2Form::Ragged2 : nx <= 768 ? X2Form::Ragged3 : X2Form::Tail;
+  }
+  return !publishing && onChunk && nx % cw == 0 ? X2Form::Col2 : X2Form::Column;
+}
+
+// The block schedule of a fused-pair sweep, decided in one place for every form: `cols` block columns (row groups x
+// column strips) of nz planes, `resident` blocks resident at once, `slots` of them for this launch
+// (slots_less_reserved).
+//   seg 0: fixed z chunks of zc planes (tune.x2sched = 0, or tune.zchunk given; auto: pick_zchunk), blocks = cols gz;
+//   seg 1: the balanced (column, plane) split over `blocks` blocks, pieces of at least 16 planes;
+//   seg 2: `parts` lockstep z parts over blocks / parts columns, the other columns as second segments;
+//   seg 3: `rounds` lockstep rounds of `parts` z parts over blocks / parts columns each (x2_lockstep_schedule).
+// The one-chunk column form never runs lockstep, the two-chunk column form only with its columns y-major
+// (!tune.x2xfast: y-adjacent columns are consecutive), the row forms always may. Pure host code, no GPU.
+struct X2SweepSchedule {
+  int seg = 1, parts = 0, rounds = 1;
+  int64_t blocks = 0;
+  int zc = 1, gz = 1;
+};
+X2SweepSchedule stencil7x2_schedule(X2Form form, int64_t cols, int nz, int64_t resident, int64_t slots,
+                                    const StencilTune &tune);
+// What stencil7x2_apply would launch for this region, kind and tune (nothing is launched; the same refusals raise; an
+// empty region reports blocks = 0): the kernel form, its in-kernel wrap variant (0 none, 1 y / z, 2 x too), the
+// schedule's inputs (slots: the occupancy query less tune.reserveCUs' share) and the schedule
+struct X2LaunchInfo {
+  X2Form form = X2Form::Column;
+  int wrapVariant = 0;
+  int64_t cols = 0, slots = 0;
+  int seg = 0, parts = 0, rounds = 1;
+  int64_t blocks = 0;
+  int zchunk = 0, gz = 0;
+};
+X2LaunchInfo stencil7x2_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind,
+                                    const Spheres &sph, const StencilTune &tune = StencilTune());
 
 // The launch schedule of a fused-triple sweep (stencil7x3), decided in one place for stencil7x3_apply, the planner
 // (stencil7x3_plan) and the tests: `cols` (row group, column) pairs of `nz` planes on `slots` resident blocks.

@@ -849,6 +849,62 @@ PYBIND11_MODULE(_C, m) {
       py::arg("slots"), py::arg("cols"), py::arg("nz"),
       "lockstep schedule of the whole-row / two-chunk-column fused pairs: (z parts per row group, blocks, rounds of "
       "whole columns); (0, 0, 1) = balanced split");
+  static const char *x2FormNames[] = {"row", "ragged2", "ragged3", "tail", "col2", "column"};
+  m.def(
+      "stencil7x2_form",
+      [](int64_t elemSize, int64_t nx, int64_t x0, int wrap, int x2row, bool publishing, int64_t bufferBytes) {
+        return x2FormNames[int(stencil7x2_form(elemSize, nx, x0, wrap, x2row, publishing, bufferBytes))];
+      },
+      py::arg("elem_size"), py::arg("nx"), py::arg("x0") = 0, py::arg("wrap") = 1, py::arg("x2row") = 1,
+      py::arg("publishing") = false, py::arg("buffer_bytes") = 0,
+      "kernel form of a fused-pair sweep (no GPU): \"row\" (512-cell periodic rows), \"ragged2\" / \"ragged3\" (257-511 / "
+      "513-768 cells), \"tail\" (769-832), \"col2\" (two-chunk columns), \"column\" (the one-chunk column kernel); x0 = "
+      "the region's first x cell counted from the first interior cell");
+  m.def(
+      "stencil7x2_schedule",
+      [](const std::string &form, int64_t cols, int nz, int64_t resident, int64_t slots, py::object tune) {
+        int f = 0;
+        while (f < 6 && form != x2FormNames[f]) ++f;
+        STENCIL_REQUIRE(f < 6, "fused-pair form " << form);
+        const X2SweepSchedule r = stencil7x2_schedule(X2Form(f), cols, nz, resident, slots,
+                                                      tune.is_none() ? StencilTune() : tune.cast<StencilTune>());
+        py::dict o;
+        o["seg"] = r.seg;
+        o["parts"] = r.parts;
+        o["rounds"] = r.rounds;
+        o["blocks"] = r.blocks;
+        o["zchunk"] = r.zc;
+        o["gz"] = r.gz;
+        return o;
+      },
+      py::arg("form"), py::arg("cols"), py::arg("nz"), py::arg("resident"), py::arg("slots"),
+      py::arg("tune") = py::none(),
+      "block schedule of a fused-pair sweep (no GPU): seg 0 = fixed z chunks (zchunk planes, gz per column), 1 = "
+      "balanced split, 2 = lockstep parts plus second segments, 3 = lockstep rounds");
+  m.def("slots_less_reserved", &slots_less_reserved, py::arg("resident"), py::arg("reserve_cus"), py::arg("cus"),
+        "resident blocks a launch may fill when it leaves reserve_cus of the device's cus CUs to another stream");
+  m.def(
+      "stencil7x2_launch_info",
+      [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &region, StencilKind kind, bool spheres,
+         const StencilTune &tune) {
+        // what stencil7x2_apply would launch (nothing is launched; the same refusals raise)
+        const Spheres s = spheres ? Spheres::jacobi(dd.get_compute_region()) : Spheres();
+        const X2LaunchInfo r = stencil7x2_launch_info(dd.domains().at(di), q, region, kind, s, tune);
+        py::dict o;
+        o["form"] = x2FormNames[int(r.form)];
+        o["wrap_variant"] = r.wrapVariant;
+        o["cols"] = r.cols;
+        o["slots"] = r.slots;
+        o["seg"] = r.seg;
+        o["parts"] = r.parts;
+        o["rounds"] = r.rounds;
+        o["blocks"] = r.blocks;
+        o["zchunk"] = r.zchunk;
+        o["gz"] = r.gz;
+        return o;
+      },
+      py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("kind"), py::arg("spheres"),
+      py::arg("tune"));
   m.def("jacobi_spheres", [](const Rect3 &cReg) {
     Spheres s = Spheres::jacobi(cReg);
     return py::make_tuple(s.hot, s.cold, s.radius);

@@ -815,23 +815,6 @@ static void launch_fast(StencilArgs<T> a, const StencilTune &tune, hipStream_t s
   HIP_CHECK(hipGetLastError());
 }
 
-// resident blocks of `kernel` over the whole device (cached per kernel)
-static int64_t resident_blocks(const void *kernel, int threads) {
-  static std::map<const void *, int64_t> cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(kernel);
-  if (it != cache.end()) return it->second;
-  int dev = 0, perCU = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, 0) != hipSuccess || perCU <= 0) perCU = 2;
-  (void)hipGetLastError();
-  const int64_t r = int64_t(perCU) * cus;
-  cache[kernel] = r;
-  return r;
-}
-
 template <typename T, int TY, int NW, int KIND, bool WRAP = false>
 static void launch_lds(StencilArgs<T> a, const StencilTune &tune, hipStream_t stream) {
   const int ny = a.hiy - a.loy, nz = a.hiz - a.loz;
@@ -849,13 +832,11 @@ static void launch_lds(StencilArgs<T> a, const StencilTune &tune, hipStream_t st
                        : tune.variant == 3 ? (const void *)stencil7_lds_kernel<T, TY, NW, KIND, true, true, false, 3>
                        : tune.variant == 4 ? (const void *)stencil7_lds_kernel<T, TY, NW, KIND, true, true, false, 4>
                                            : (const void *)stencil7_lds_kernel<T, TY, NW, KIND, true, true, false>;
-    int64_t targetBlocks = resident_blocks(kern, 64 * NW);
+    int64_t targetBlocks = resident_blocks(kern, 64 * NW, 2);
     if (tune.reserveCUs > 0) { // leave that many CUs to the comm stream's kernels (overlapped steps)
-      int cus = 256, dev = 0; // the device the launch goes to (the caller set it: dom.set_device())
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-      const int64_t perCU = std::max<int64_t>(1, targetBlocks / std::max(1, cus));
-      targetBlocks = std::max<int64_t>(perCU, targetBlocks - perCU * std::min(tune.reserveCUs, cus / 2));
+      int dev = 0;             // the device the launch goes to (the caller set it: dom.set_device())
+      (void)hipGetDevice(&dev);
+      targetBlocks = launch_slots(targetBlocks, tune.reserveCUs, dev);
     }
     const int64_t nzc = std::max<int64_t>(1, targetBlocks / cols);
     zc = int(std::max<int64_t>(16, (nz + nzc - 1) / nzc));
@@ -911,8 +892,7 @@ static void apply_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, con
   const int off = ((a.lox - rxm) % V + V) % V;
   a.x0 = a.lox - off;
   a.nchunks = (a.hix - a.x0 + V - 1) / V;
-  const bool alignedLayout = (reinterpret_cast<uintptr_t>(a.src + a.x0) % 16 == 0) &&
-                             (reinterpret_cast<uintptr_t>(a.dst + a.x0) % 16 == 0) && ((a.px * int64_t(sizeof(T))) % 16 == 0);
+  const bool alignedLayout = aligned_vector_layout(dom, qi, a.x0);
   // vector loads and the right-edge neighbour stay inside the padded row (LocalDomain keeps >= V+1 tail elements)
   const bool fits = a.x0 + int64_t(a.nchunks) * V < dom.row_limit(qi);
   dom.set_device();
@@ -923,12 +903,7 @@ static void apply_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, con
     STENCIL_REQUIRE((tune.wrap & ~stencil7_wrappable_axes(dom, qi)) == 0,
                     "in-kernel wrap " << tune.wrap << " not supported by this layout (" << stencil7_wrappable_axes(dom, qi)
                                       << ")");
-    const Rect3 cr = dom.get_compute_region();
-    const int64_t lo[3] = {region.lo.x, region.lo.y, region.lo.z}, hi[3] = {region.hi.x, region.hi.y, region.hi.z};
-    const int64_t clo[3] = {cr.lo.x, cr.lo.y, cr.lo.z}, chi[3] = {cr.hi.x, cr.hi.y, cr.hi.z};
-    for (int ax = 0; ax < 3; ++ax)
-      STENCIL_REQUIRE(!((tune.wrap >> ax) & 1) || (lo[ax] == clo[ax] && hi[ax] == chi[ax]),
-                      "region " << region << " does not span wrapped axis " << ax << " of " << cr);
+    require_wrap_spans(dom, region, tune.wrap);
     STENCIL_REQUIRE(alignedLayout && fits && a.x0 == a.lox,
                     "in-kernel wrap needs the aligned vector layout (aligned " << alignedLayout << ", fits " << fits
                                                                                << ", x0 " << a.x0 << ", lox " << a.lox
@@ -976,18 +951,12 @@ static void apply_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, con
 }
 
 int stencil7_wrappable_axes(const LocalDomain &dom, int64_t qi) {
-  if (dom.backend() != Backend::Device) return 0;
-  const DType dt = dom.dtype(qi);
-  const int64_t es = dom.elem_size(qi);
-  if (!(dt == DType::F32 || dt == DType::F64 || (dt == DType::Bytes && (es == 4 || es == 8)))) return 0;
+  int64_t es = 0;
+  if (dom.backend() != Backend::Device || !fp_quantity(dom, qi, &es)) return 0;
   const int64_t V = 16 / es;
   const int64_t lox = dom.radius().x(-1), nx = dom.size().x;
-  const Dim3 p = dom.pitch(qi);
   // the chunk grid starts at lox (16-B aligned) and the vector loads stay inside the padded row (apply_t's `fits`)
-  const bool aligned = (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.curr_data(qi)) + lox * es) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.next_data(qi)) + lox * es) % 16 == 0) &&
-                       (p.x * es) % 16 == 0;
-  if (!aligned || lox + (nx + V - 1) / V * V >= dom.row_limit(qi)) return 0;
+  if (!aligned_vector_layout(dom, qi, lox) || lox + (nx + V - 1) / V * V >= dom.row_limit(qi)) return 0;
   // x: whole chunks (the last chunk's right edge is the face); y / z: one conditional shift per access
   return (nx % V == 0 ? 1 : 0) | 2 | 4;
 }
@@ -997,10 +966,7 @@ void stencil7_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, Ste
   STENCIL_REQUIRE(dom.radius().x(-1) >= 1 && dom.radius().x(1) >= 1 && dom.radius().y(-1) >= 1 &&
                       dom.radius().y(1) >= 1 && dom.radius().z(-1) >= 1 && dom.radius().z(1) >= 1,
                   "7-point stencil needs face radii >= 1");
-  const Rect3 cr = dom.get_compute_region();
-  STENCIL_REQUIRE(region.empty() || (cr.contains(region.lo) && region.hi.all_ge(region.lo) &&
-                                     region.hi.x <= cr.hi.x && region.hi.y <= cr.hi.y && region.hi.z <= cr.hi.z),
-                  "stencil region " << region << " outside compute region " << cr);
+  require_region_in_compute(dom, region);
   if (tune.variant == StencilTune::kMfma) {
     STENCIL_REQUIRE(fwd == nullptr, "the MFMA variant does not forward halos");
     STENCIL_REQUIRE(tune.wrap == 0, "the MFMA variant reads halos (no in-kernel wrap)");
@@ -1034,8 +1000,7 @@ static void apply_regions_t(const LocalDomain &dom, int64_t qi, const std::vecto
   a.wrapm = wrap;
   const Dim3 org = dom.accessor_origin();
   const int rxm = int(dom.radius().x(-1));
-  const bool aligned = (reinterpret_cast<uintptr_t>(a.src + rxm) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(a.dst + rxm) % 16 == 0) && ((a.px * int64_t(sizeof(T))) % 16 == 0);
+  const bool aligned = aligned_vector_layout(dom, qi, rxm);
   std::vector<Rect3> rs;
   for (const auto &r : regions)
     if (!r.empty()) rs.push_back(Rect3(r.lo - org, r.hi - org));
@@ -1105,11 +1070,7 @@ void stencil7_apply_regions(const LocalDomain &dom, int64_t qi, const std::vecto
   }
   STENCIL_REQUIRE((tune.wrap & ~stencil7_wrappable_axes(dom, qi)) == 0,
                   "in-kernel wrap " << tune.wrap << " not supported by this layout");
-  for (const auto &r : regions) {
-    const Rect3 cr = dom.get_compute_region();
-    STENCIL_REQUIRE(r.empty() || (cr.contains(r.lo) && r.hi.x <= cr.hi.x && r.hi.y <= cr.hi.y && r.hi.z <= cr.hi.z),
-                    "stencil region " << r << " outside compute region " << cr);
-  }
+  for (const auto &r : regions) require_region_in_compute(dom, r);
   dom.set_device();
   const bool f64 = dom.elem_size(qi) == 8;
   if (!f64)
@@ -1123,12 +1084,6 @@ void stencil7_apply_regions(const LocalDomain &dom, int64_t qi, const std::vecto
 // ---------------------------------------------------------------------------------------------------------
 // halo forwarder tables
 // ---------------------------------------------------------------------------------------------------------
-static bool fp_quantity(const LocalDomain &dom, int64_t qi, int64_t *es) {
-  const DType dt = dom.dtype(qi);
-  *es = dom.elem_size(qi);
-  return dt == DType::F32 || dt == DType::F64 || (dt == DType::Bytes && (*es == 4 || *es == 8));
-}
-
 bool HaloForwarder::supported(const LocalDomain &dom, int64_t qi) {
   int64_t es = 0;
   if (dom.backend() != Backend::Device || !fp_quantity(dom, qi, &es)) return false;
@@ -1140,14 +1095,10 @@ bool HaloForwarder::supported(const LocalDomain &dom, int64_t qi) {
   if (sz.x < 2 * (16 / std::max<int64_t>(es, 1)) + r.x(1) + r.x(-1)) return false;
   // same layout checks as the vector kernel (apply_t)
   const int64_t V = 16 / es;
-  const Dim3 p = dom.pitch(qi);
   const int64_t lox = r.x(-1), hix = lox + sz.x;
   const int64_t x0 = lox - ((lox - r.x(-1)) % V + V) % V;
   const int64_t nchunks = (hix - x0 + V - 1) / V;
-  const bool aligned = (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.curr_data(qi)) + x0 * es) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.next_data(qi)) + x0 * es) % 16 == 0) &&
-                       (p.x * es) % 16 == 0;
-  return aligned && x0 + nchunks * V < dom.row_limit(qi);
+  return aligned_vector_layout(dom, qi, x0) && x0 + nchunks * V < dom.row_limit(qi);
 }
 
 HaloForwarder::HaloForwarder(const LocalDomain &src, int64_t qi, const std::vector<ForwardTarget> &targets) {

@@ -19,8 +19,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -1127,39 +1125,18 @@ __global__ __launch_bounds__(256) void stencil7x2_thin_kernel(StencilArgs<T> a, 
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static int64_t x2_resident_blocks(const void *kernel, int threads) {
-  static std::map<const void *, int64_t> cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(kernel);
-  if (it != cache.end()) return it->second;
-  int dev = 0, perCU = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, 0) != hipSuccess || perCU <= 0) perCU = 1;
-  (void)hipGetLastError();
-  const int64_t r = int64_t(perCU) * cus;
-  cache[kernel] = r;
-  return r;
-}
-
 bool stencil7x2_supported(const LocalDomain &dom, int64_t qi) {
-  if (dom.backend() != Backend::Device) return false;
-  const DType dt = dom.dtype(qi);
-  const int64_t es = dom.elem_size(qi);
-  if (!(dt == DType::F32 || dt == DType::F64 || (dt == DType::Bytes && (es == 4 || es == 8)))) return false;
+  int64_t es = 0;
+  if (dom.backend() != Backend::Device || !fp_quantity(dom, qi, &es)) return false;
   const Radius &r = dom.radius();
   for (int s = -1; s <= 1; s += 2)
     if (r.x(s) < 2 || r.y(s) < 2 || r.z(s) < 2) return false;
   const int64_t V = 16 / es;
-  const Dim3 p = dom.pitch(qi);
   const int64_t lox = r.x(-1), hix = lox + dom.size().x;
   const int64_t nchunks = (hix - lox + V - 1) / V;
-  const bool aligned = (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.curr_data(qi)) + lox * es) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.next_data(qi)) + lox * es) % 16 == 0) &&
-                       (p.x * es) % 16 == 0;
   // the edge lanes read x-2 and x+V+1 of their chunk: stay inside the padded row
-  return aligned && lox - 2 + dom.front_slack(qi) >= 0 && lox + nchunks * V + 1 < dom.row_limit(qi);
+  return aligned_vector_layout(dom, qi, lox) && lox - 2 + dom.front_slack(qi) >= 0 &&
+         lox + nchunks * V + 1 < dom.row_limit(qi);
 }
 
 int stencil7x2_wrappable_axes(const LocalDomain &dom, int64_t qi, int x2row) {
@@ -1168,7 +1145,7 @@ int stencil7x2_wrappable_axes(const LocalDomain &dom, int64_t qi, int x2row) {
   const int64_t lox = dom.radius().x(-1), nx = dom.size().x, lim = dom.row_limit(qi), slack = dom.front_slack(qi);
   // ragged fp32 rows of 257-832 cells: the whole-row kernel wraps x by broadcasting the row-end cells (a ragged last
   // chunk reads at most 3 cells past the row end, inside the padded row; rows of 769-832 end in per-lane tail cells)
-  const bool rowX = x2row != 0 && es == 4 && nx > 256 && nx <= 832 && lox + (nx + V - 1) / V * V < lim;
+  const bool rowX = x2row != 0 && es == 4 && x2_row_width(nx) && lox + (nx + V - 1) / V * V < lim;
   if (rowX && nx % V != 0) return 1 | (dom.size().y >= 2 ? 2 : 0) | (dom.size().z >= 2 ? 4 : 0);
   // x: whole chunks only (the chunk grid starts at the 16-B aligned lox), at least two, and the last chunk not on
   // lane 0 of its column (a wrap lane shifts both of its edge pairs: its other edge must be the unused one, never a
@@ -1179,284 +1156,221 @@ int stencil7x2_wrappable_axes(const LocalDomain &dom, int64_t qi, int x2row) {
   return (x ? 1 : 0) | (dom.size().y >= 2 ? 2 : 0) | (dom.size().z >= 2 ? 4 : 0);
 }
 
-// along wrapped axes the region must be the whole compute region (the kernels wrap at its faces)
 static void check_wrap(const LocalDomain &dom, int64_t qi, const Rect3 &region, int wrap, int x2row) {
   if (wrap == 0) return;
   STENCIL_REQUIRE((wrap & ~stencil7x2_wrappable_axes(dom, qi, x2row)) == 0,
                   "in-kernel wrap " << wrap << " not supported by this layout ("
                                     << stencil7x2_wrappable_axes(dom, qi, x2row) << ")");
-  const Rect3 cr = dom.get_compute_region();
-  const int64_t lo[3] = {region.lo.x, region.lo.y, region.lo.z}, hi[3] = {region.hi.x, region.hi.y, region.hi.z};
-  const int64_t clo[3] = {cr.lo.x, cr.lo.y, cr.lo.z}, chi[3] = {cr.hi.x, cr.hi.y, cr.hi.z};
-  for (int ax = 0; ax < 3; ++ax)
-    STENCIL_REQUIRE(!((wrap >> ax) & 1) || (lo[ax] == clo[ax] && hi[ax] == chi[ax]),
-                    "region " << region << " does not span wrapped axis " << ax << " of " << cr);
+  require_wrap_spans(dom, region, wrap);
 }
 
-template <typename T, int KIND, int NW, int PF>
-static void apply_x2_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph, hipStream_t stream,
-                       const StencilTune &tune) {
-  constexpr int V = Vec16<T>::N, YO = NW - 4;
-  StencilArgs<T> a = make_args<T>(dom, qi, region, KIND == 0 ? StencilKind::Jacobi : StencilKind::Astaroth, sph);
-  a.flip = tune.alternateZ ? (dom.parity() & 1) : 0;
-  a.nt = tune.nontemporal ? 1 : 0;
-  a.wrapm = tune.wrap;
-  a.xfast = tune.x2xfast;
+// The sweep kernels' instances, by form (X2Form), in-kernel wrap variant wv (0 none, 1 y / z, 2 x too) and boundary-
+// plane publication. All run 12 waves (one src row each, 8 output rows) and one plane of z lookahead: the one-chunk
+// column kernel's measured best (bench.py 12x3 883-888, 12x1 881-883, 16x2 797-804, 8x2 759-772 Gcells/s,
+// profiles/r1s4_bench_block_shapes.txt; the other shapes were removed in r6); the row kernel measured 1-3 planes
+// within noise once the edge waves skip u1 / u2 (r2s3; 2 / 3 removed in r6); two planes would spill the Jacobi
+// instance of the two-chunk column kernel (the row kernel shows no difference).
+constexpr int kX2NW = 12, kX2PF = 1;
+template <typename T> using X2ColumnKernel = void (*)(StencilArgs<T>);
+template <typename T> using X2TableKernel = void (*)(StencilArgs<T>, ZPartBounds);
+template <typename T, int KIND> static X2ColumnKernel<T> x2_column_kernel(int wv) {
+  return wv == 2   ? stencil7x2_kernel<T, kX2NW, kX2PF, KIND, 2>
+         : wv == 1 ? stencil7x2_kernel<T, kX2NW, kX2PF, KIND, 1>
+                   : stencil7x2_kernel<T, kX2NW, kX2PF, KIND, 0>;
+}
+template <typename T, int KIND> static X2TableKernel<T> x2_col2_kernel(int wv) {
+  return wv == 2   ? stencil7x2_col2_kernel<T, kX2NW, kX2PF, KIND, 2>
+         : wv == 1 ? stencil7x2_col2_kernel<T, kX2NW, kX2PF, KIND, 1>
+                   : stencil7x2_col2_kernel<T, kX2NW, kX2PF, KIND, 0>;
+}
+// H chunks per lane; RAG: rows shorter than 256 H cells; TL: one tail cell per lane beyond them
+template <int KIND, int H, bool RAG, bool TL> static X2TableKernel<float> x2_row_instance(bool pub) {
+  return pub ? stencil7x2_row_kernel<kX2NW, kX2PF, KIND, H, RAG, TL, true>
+             : stencil7x2_row_kernel<kX2NW, kX2PF, KIND, H, RAG, TL, false>;
+}
+template <int KIND> static X2TableKernel<float> x2_row_kernel(X2Form form, bool pub) {
+  switch (form) {
+  case X2Form::Row: return x2_row_instance<KIND, 2, false, false>(pub);
+  case X2Form::Ragged2: return x2_row_instance<KIND, 2, true, false>(pub);
+  case X2Form::Ragged3: return x2_row_instance<KIND, 3, true, false>(pub);
+  default: return x2_row_instance<KIND, 3, false, true>(pub); // X2Form::Tail
+  }
+}
+
+// the block schedule of a sweep (stencil_ops.hpp): the one decision every form shares
+X2SweepSchedule stencil7x2_schedule(X2Form form, int64_t cols, int nz, int64_t resident, int64_t slots,
+                                    const StencilTune &tune) {
+  X2SweepSchedule r;
+  if (tune.x2sched == 0 || tune.zchunk > 0) {
+    r.seg = 0;
+    // each z-chunk re-reads 4 warm-up planes (2 src + 2 for u1)
+    r.zc = tune.zchunk > 0 ? tune.zchunk : pick_zchunk(cols, nz, resident, 4, 16);
+    r.gz = (nz + r.zc - 1) / r.zc;
+    r.blocks = cols * r.gz;
+    return r;
+  }
+  // one block per resident slot, but pieces of at least 16 planes (each piece re-reads 4 warm-up planes)
+  r.blocks = std::max<int64_t>(1, std::min<int64_t>(slots, cols * nz / 16));
+  // lockstep parts (seg 2 / 3, x2_lockstep_schedule): with 8 CUs left to the transports (248 blocks) the balanced
+  // split puts y-adjacent blocks 16 planes apart and their halo rows miss L2 (512^3 local interior: 276 vs 237 us
+  // at 256 blocks); 813x407x407 (51 row groups) runs 5 parts on 255 blocks. Two-chunk columns: only when y-adjacent
+  // columns are consecutive (column index y-major)
+  const bool lockstep = x2_row_form(form) || (form == X2Form::Col2 && !tune.x2xfast);
+  if (!tune.x2lockstep || !lockstep) return r;
+  const X2Schedule ls = x2_lockstep_schedule(slots, cols, nz);
+  if (ls.parts > 0) {
+    r.seg = ls.rounds > 1 ? 3 : 2;
+    r.parts = ls.parts;
+    r.rounds = ls.rounds;
+    r.blocks = ls.blocks;
+  }
+  return r;
+}
+
+// a sweep ready to launch: the kernel's arguments, the z-part table, the grid and what decided them
+template <typename T> struct X2Launch {
+  StencilArgs<T> a;
+  ZPartBounds zb;
+  uint32_t blocks;
+  X2Form form;
+  int wv;
+  int64_t cols, slots;
+};
+// everything stencil7x2_apply decides before the launch (stencil7x2_launch_info reports it without launching)
+template <typename T, int KIND>
+static X2Launch<T> x2_prepare(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph,
+                              const StencilTune &tune) {
+  constexpr int V = Vec16<T>::N, YO = kX2NW - 4;
+  X2Launch<T> L{};
+  StencilArgs<T> &a = L.a;
+  a = make_args<T>(dom, qi, region, KIND == 0 ? StencilKind::Jacobi : StencilKind::Astaroth, sph);
   const int rxm = int(dom.radius().x(-1));
-  const int off = ((a.lox - rxm) % V + V) % V;
-  a.x0 = a.lox - off;
-  a.nchunks = (a.hix - a.x0 + V - 1) / V;
-  const int ny = a.hiy - a.loy, nz = a.hiz - a.loz;
-  a.gx = (a.nchunks + 63) / 64;
-  a.gy = (ny + YO - 1) / YO;
-  a.remap = tune.xcdRemap ? 1 : 0;
-  const void *kern = (const void *)stencil7x2_kernel<T, NW, PF, KIND, 0>;
-  const int64_t cols = int64_t(a.gx) * a.gy;
-  const int64_t resident = x2_resident_blocks(kern, 64 * NW);
-  uint32_t blocks;
-  if (tune.x2sched != 0 && tune.zchunk <= 0) {
-    // one block per resident slot, but pieces of at least 16 planes (each piece re-reads 4 warm-up planes)
-    a.seg = 1;
-    a.zc = 1;
-    a.gz = 1;
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dom.gpu()) != hipSuccess) cus = 256;
-    const int64_t perCU = std::max<int64_t>(1, resident / std::max(1, cus));
-    const int64_t slots = std::max<int64_t>(perCU, resident - perCU * std::min(tune.reserveCUs, cus / 2));
-    blocks = uint32_t(std::max<int64_t>(1, std::min<int64_t>(slots, cols * nz / 16)));
-  } else {
-    int zc = tune.zchunk;
-    if (zc <= 0) // each z-chunk re-reads 4 warm-up planes (2 src + 2 for u1)
-      zc = pick_zchunk(cols, nz, resident, 4, 16);
-    a.zc = zc;
-    a.gz = (nz + zc - 1) / zc;
-    blocks = uint32_t(cols * a.gz);
-  }
-  dom.set_device();
-  if (a.wrapm & 1)
-    hipLaunchKernelGGL((stencil7x2_kernel<T, NW, PF, KIND, 2>), dim3(blocks), dim3(64, NW), 0, stream, a);
-  else if (a.wrapm)
-    hipLaunchKernelGGL((stencil7x2_kernel<T, NW, PF, KIND, 1>), dim3(blocks), dim3(64, NW), 0, stream, a);
-  else
-    hipLaunchKernelGGL((stencil7x2_kernel<T, NW, PF, KIND, 0>), dim3(blocks), dim3(64, NW), 0, stream, a);
-  HIP_CHECK(hipGetLastError());
-}
-
-// whole-row kernel: fp32, x wrapped in-kernel, rows starting on a 16-B chunk; H chunks per lane (RAG: rows shorter
-// than 256 H cells)
-template <int KIND, int PF, int H = 2, bool RAG = false, int NW = 12, bool TL = false>
-static bool apply_x2row_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph, hipStream_t stream,
-                          const StencilTune &tune) {
-  constexpr int YO = NW - 4;
-  StencilArgs<float> a = make_args<float>(dom, qi, region, KIND == 0 ? StencilKind::Jacobi : StencilKind::Astaroth, sph);
-  const int rxm = int(dom.radius().x(-1));
-  const int nx = a.hix - a.lox;
-  const bool fitsH = TL ? (nx > 256 * H && nx <= 256 * H + 64) : (RAG ? (nx > 256 * (H - 1) && nx <= 256 * H) : nx == 512);
-  if (!(tune.wrap & 1) || !fitsH || (a.lox - rxm) % 4 != 0) return false;
-  if (dom.buffer_bytes(qi) >= (int64_t(1) << 32) - 4096) return false; // 32-bit buffer-load offsets
+  const int nx = a.hix - a.lox, ny = a.hiy - a.loy, nz = a.hiz - a.loz;
+  L.form = stencil7x2_form(int64_t(sizeof(T)), nx, a.lox - rxm, tune.wrap, tune.x2row, tune.publish != nullptr,
+                           dom.buffer_bytes(qi));
+  STENCIL_REQUIRE(!tune.publish || x2_row_form(L.form), "boundary-plane publication needs the whole-row kernel");
+  // the column kernels wrap x only for whole chunks (ragged periodic rows are the whole-row kernel's)
+  STENCIL_REQUIRE(L.form != X2Form::Column || !(tune.wrap & 1) || (stencil7x2_wrappable_axes(dom, qi, 0) & 1),
+                  "in-kernel x wrap of a ragged row needs the whole-row kernel (fp32, x2row, 256 < nx < 1024)");
+  L.wv = (tune.wrap & 1) ? 2 : (tune.wrap ? 1 : 0);
   a.flip = tune.alternateZ ? (dom.parity() & 1) : 0;
   a.nt = tune.nontemporal ? 1 : 0;
   a.wrapm = tune.wrap;
-  a.early = tune.x2early ? 1 : 0;
-  a.x0 = a.lox;
-  a.nchunks = 128;
   a.remap = tune.xcdRemap ? 1 : 0;
-  const int ny = a.hiy - a.loy, nz = a.hiz - a.loz;
-  if (tune.publish) {
-    a.pub = reinterpret_cast<unsigned long long *>(tune.publish);
-    a.pubLo = a.loz + tune.publishDepth;
-    a.pubHi = a.hiz - tune.publishDepth;
-  }
-  a.gx = 1;
   a.gy = (ny + YO - 1) / YO;
-  const void *kern = (const void *)stencil7x2_row_kernel<NW, PF, KIND, H, RAG, TL>;
-  const int64_t cols = a.gy;
-  const int64_t resident = x2_resident_blocks(kern, 64 * NW);
-  uint32_t blocks;
-  if (tune.x2sched != 0 && tune.zchunk <= 0) {
-    a.seg = 1;
-    a.zc = 1;
-    a.gz = 1;
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dom.gpu()) != hipSuccess) cus = 256;
-    const int64_t perCU = std::max<int64_t>(1, resident / std::max(1, cus));
-    const int64_t slots = std::max<int64_t>(perCU, resident - perCU * std::min(tune.reserveCUs, cus / 2));
-    blocks = uint32_t(std::max<int64_t>(1, std::min<int64_t>(slots, cols * nz / 16)));
-    // lockstep parts (a.seg = 2, x2_lockstep_schedule): with 8 CUs left to the transports (248 blocks) the balanced
-    // split puts y-adjacent blocks 16 planes apart and their halo rows miss L2 (512^3 local interior: 276 vs 237 us
-    // at 256 blocks); 813x407x407 (51 row groups) runs 5 parts on 255 blocks
-    const X2Schedule ls = x2_lockstep_schedule(slots, cols, nz);
-    if (tune.x2lockstep && ls.parts > 0) {
-      a.seg = ls.rounds > 1 ? 3 : 2;
-      a.zparts = ls.parts;
-      a.zrounds = ls.rounds;
-      blocks = uint32_t(ls.blocks);
+  const void *kern = nullptr; // the instance the occupancy query is made for
+  if (L.form == X2Form::Column) {
+    a.xfast = tune.x2xfast;
+    a.x0 = a.lox - ((a.lox - rxm) % V + V) % V; // chunk grid anchored at the 16-B aligned interior start
+    a.nchunks = (a.hix - a.x0 + V - 1) / V;
+    a.gx = (a.nchunks + 63) / 64;
+    kern = (const void *)x2_column_kernel<T, KIND>(0);
+  } else if (L.form == X2Form::Col2) {
+    a.xfast = tune.x2xfast;
+    a.early = tune.x2early ? 1 : 0;
+    a.x0 = a.lox; // on a 16-B chunk (stencil7x2_form)
+    a.nchunks = nx / V;
+    a.gx = nx / (128 * V);
+    kern = (const void *)x2_col2_kernel<T, KIND>(L.wv);
+  } else if constexpr (std::is_same<T, float>::value) {
+    a.early = tune.x2early ? 1 : 0;
+    a.x0 = a.lox;
+    a.nchunks = 128;
+    a.gx = 1;
+    if (tune.publish) {
+      a.pub = reinterpret_cast<unsigned long long *>(tune.publish);
+      a.pubLo = a.loz + tune.publishDepth;
+      a.pubHi = a.hiz - tune.publishDepth;
     }
-  } else {
-    int zc = tune.zchunk;
-    if (zc <= 0) zc = pick_zchunk(cols, nz, resident, 4, 16);
-    a.zc = zc;
-    a.gz = (nz + zc - 1) / zc;
-    blocks = uint32_t(cols * a.gz);
+    kern = (const void *)x2_row_kernel<KIND>(L.form, false);
   }
-  dom.set_device();
-  ZPartBounds zb{};
-  zb.on = 0;
-  if (KIND == 0 && a.seg == 2) sphere_part_bounds(zb, a, int64_t(blocks) / a.zparts, a.zparts, NW, YO, 2, tune.x2sphw);
-  if (a.pub)
-    hipLaunchKernelGGL((stencil7x2_row_kernel<NW, PF, KIND, H, RAG, TL, true>), dim3(blocks), dim3(64, NW), 0, stream, a,
-                       zb);
-  else
-    hipLaunchKernelGGL((stencil7x2_row_kernel<NW, PF, KIND, H, RAG, TL>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
-  HIP_CHECK(hipGetLastError());
-  return true;
-}
-
-// two-chunk column kernel: the region's x extent a whole number of CW-cell columns (512 fp32, 256 fp64) starting on
-// a 16-B chunk
-template <typename T, int KIND, int PF, int WRAP>
-static void apply_x2col2_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph,
-                           hipStream_t stream, const StencilTune &tune) {
-  constexpr int NW = 12, YO = NW - 4, V = int(16 / sizeof(T)), CW = 128 * V;
-  StencilArgs<T> a = make_args<T>(dom, qi, region, KIND == 0 ? StencilKind::Jacobi : StencilKind::Astaroth, sph);
-  a.flip = tune.alternateZ ? (dom.parity() & 1) : 0;
-  a.nt = tune.nontemporal ? 1 : 0;
-  a.wrapm = tune.wrap;
-  a.xfast = tune.x2xfast;
-  a.remap = tune.xcdRemap ? 1 : 0;
-  a.early = tune.x2early ? 1 : 0;
-  a.x0 = a.lox; // 16-B aligned (checked by the caller)
-  a.nchunks = (a.hix - a.x0) / V;
-  const int ny = a.hiy - a.loy, nz = a.hiz - a.loz;
-  a.gx = (a.hix - a.x0) / CW;
-  a.gy = (ny + YO - 1) / YO;
-  const void *kern = (const void *)stencil7x2_col2_kernel<T, NW, PF, KIND, WRAP>;
-  const int64_t cols = int64_t(a.gx) * a.gy;
-  const int64_t resident = x2_resident_blocks(kern, 64 * NW);
-  uint32_t blocks;
-  if (tune.x2sched != 0 && tune.zchunk <= 0) {
-    a.seg = 1;
-    a.zc = 1;
-    a.gz = 1;
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dom.gpu()) != hipSuccess) cus = 256;
-    const int64_t perCU = std::max<int64_t>(1, resident / std::max(1, cus));
-    const int64_t slots = std::max<int64_t>(perCU, resident - perCU * std::min(tune.reserveCUs, cus / 2));
-    blocks = uint32_t(std::max<int64_t>(1, std::min<int64_t>(slots, cols * nz / 16)));
-    // lockstep parts (x2_lockstep_schedule) when y-adjacent columns are consecutive (column index y-major)
-    const X2Schedule ls = x2_lockstep_schedule(slots, cols, nz);
-    if (tune.x2lockstep && !tune.x2xfast && ls.parts > 0) {
-      a.seg = ls.rounds > 1 ? 3 : 2;
-      a.zparts = ls.parts;
-      a.zrounds = ls.rounds;
-      blocks = uint32_t(ls.blocks);
-    }
-  } else {
-    int zc = tune.zchunk;
-    if (zc <= 0) zc = pick_zchunk(cols, nz, resident, 4, 16);
-    a.zc = zc;
-    a.gz = (nz + zc - 1) / zc;
-    blocks = uint32_t(cols * a.gz);
+  L.cols = int64_t(a.gx) * a.gy;
+  const int64_t resident = resident_blocks(kern, 64 * kX2NW, 1);
+  L.slots = launch_slots(resident, tune.reserveCUs, dom.gpu());
+  const X2SweepSchedule s = stencil7x2_schedule(L.form, L.cols, nz, resident, L.slots, tune);
+  a.seg = s.seg;
+  a.zc = s.zc;
+  a.gz = s.gz;
+  if (s.seg >= 2) {
+    a.zparts = s.parts;
+    a.zrounds = s.rounds;
   }
-  dom.set_device();
-  ZPartBounds zb{};
-  zb.on = 0;
+  L.blocks = uint32_t(s.blocks);
+  // sphere-weighted z-part bounds: Jacobi lockstep parts of a single column strip (every row form; one two-chunk column)
   if (KIND == 0 && a.seg == 2 && a.gx == 1)
-    sphere_part_bounds(zb, a, int64_t(blocks) / a.zparts, a.zparts, NW, YO, 2, tune.x2sphw);
-  hipLaunchKernelGGL((stencil7x2_col2_kernel<T, NW, PF, KIND, WRAP>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
+    sphere_part_bounds(L.zb, a, int64_t(L.blocks) / a.zparts, a.zparts, kX2NW, YO, 2, tune.x2sphw);
+  return L;
+}
+
+// launches the sweep, or with `info` reports it instead
+template <typename T, int KIND>
+static void x2_run_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph, hipStream_t stream,
+                     const StencilTune &tune, X2LaunchInfo *info) {
+  const X2Launch<T> L = x2_prepare<T, KIND>(dom, qi, region, sph, tune);
+  const StencilArgs<T> &a = L.a;
+  if (info) {
+    info->form = L.form;
+    info->wrapVariant = L.wv;
+    info->cols = L.cols;
+    info->slots = L.slots;
+    info->seg = a.seg;
+    info->parts = a.seg >= 2 ? a.zparts : 0;
+    info->rounds = a.seg == 3 ? a.zrounds : 1;
+    info->blocks = int64_t(L.blocks);
+    info->zchunk = a.zc;
+    info->gz = a.gz;
+    return;
+  }
+  dom.set_device();
+  const dim3 grid(L.blocks), block(64, kX2NW);
+  if (L.form == X2Form::Column) {
+    const X2ColumnKernel<T> k = x2_column_kernel<T, KIND>(L.wv);
+    hipLaunchKernelGGL(k, grid, block, 0, stream, a);
+  } else if (L.form == X2Form::Col2) {
+    const X2TableKernel<T> k = x2_col2_kernel<T, KIND>(L.wv);
+    hipLaunchKernelGGL(k, grid, block, 0, stream, a, L.zb);
+  } else if constexpr (std::is_same<T, float>::value) {
+    const X2TableKernel<float> k = x2_row_kernel<KIND>(L.form, a.pub != nullptr);
+    hipLaunchKernelGGL(k, grid, block, 0, stream, a, L.zb);
+  }
   HIP_CHECK(hipGetLastError());
 }
 
-template <typename T, int KIND, int PF>
-static void apply_x2col2_wrap(const LocalDomain &dom, int64_t qi, const Rect3 &region, const Spheres &sph,
-                              hipStream_t stream, const StencilTune &tune) {
-  if (tune.wrap & 1)
-    apply_x2col2_t<T, KIND, PF, 2>(dom, qi, region, sph, stream, tune);
-  else if (tune.wrap)
-    apply_x2col2_t<T, KIND, PF, 1>(dom, qi, region, sph, stream, tune);
+// checks, then the sweep of the quantity's type and kind
+static void x2_run(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind, const Spheres &sph,
+                   hipStream_t stream, const StencilTune &tune, X2LaunchInfo *info) {
+  if (region.empty()) return;
+  STENCIL_REQUIRE(stencil7x2_supported(dom, qi),
+                  "two-step stencil needs a device fp32/fp64 quantity, face radii >= 2 and the aligned layout");
+  require_region_in_compute(dom, region);
+  check_wrap(dom, qi, region, tune.wrap, tune.x2row);
+  const bool jac = kind == StencilKind::Jacobi;
+  if (dom.elem_size(qi) == 4)
+    jac ? x2_run_t<float, 0>(dom, qi, region, sph, stream, tune, info)
+        : x2_run_t<float, 1>(dom, qi, region, sph, stream, tune, info);
   else
-    apply_x2col2_t<T, KIND, PF, 0>(dom, qi, region, sph, stream, tune);
-}
-
-bool stencil7x2_row_kernel_used(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StencilTune &tune) {
-  if (region.empty() || !stencil7x2_supported(dom, qi) || dom.elem_size(qi) != 4 || !tune.x2row || !(tune.wrap & 1))
-    return false;
-  const Rect3 rr(region.lo - dom.accessor_origin(), region.hi - dom.accessor_origin());
-  const int64_t nx = rr.hi.x - rr.lo.x;
-  return (nx == 512 || (nx > 256 && nx <= 832)) && (rr.lo.x - dom.radius().x(-1)) % 4 == 0 &&
-         dom.buffer_bytes(qi) < (int64_t(1) << 32) - 4096;
+    jac ? x2_run_t<double, 0>(dom, qi, region, sph, stream, tune, info)
+        : x2_run_t<double, 1>(dom, qi, region, sph, stream, tune, info);
 }
 
 void stencil7x2_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind, const Spheres &sph,
                       hipStream_t stream, const StencilTune &tune) {
-  if (region.empty()) return;
-  STENCIL_REQUIRE(stencil7x2_supported(dom, qi),
-                  "two-step stencil needs a device fp32/fp64 quantity, face radii >= 2 and the aligned layout");
-  const Rect3 cr = dom.get_compute_region();
-  STENCIL_REQUIRE(cr.contains(region.lo) && region.hi.x <= cr.hi.x && region.hi.y <= cr.hi.y && region.hi.z <= cr.hi.z,
-                  "stencil region " << region << " outside compute region " << cr);
-  check_wrap(dom, qi, region, tune.wrap, tune.x2row);
-  const bool f32 = dom.elem_size(qi) == 4;
-  const bool jac = kind == StencilKind::Jacobi;
-  if (f32 && tune.x2row) { // whole rows of 512 cells in one wave (x wrapped in-kernel)
-    // one plane of lookahead (1-3 measured within noise once the edge waves skip u1 / u2, r2s3; 2 / 3 removed in r6)
-    bool done = jac ? apply_x2row_t<0, 1>(dom, qi, region, sph, stream, tune)
-                    : apply_x2row_t<1, 1>(dom, qi, region, sph, stream, tune);
-    if (done) return;
-    const Rect3 rr(region.lo - dom.accessor_origin(), region.hi - dom.accessor_origin());
-    const int64_t nx = rr.hi.x - rr.lo.x;
-    // ragged periodic rows (x wrapped, 256 < nx <= 768 but not 512): H = 2 / 3 chunks per lane, first / last cell
-    // broadcast for the wrap (one plane of lookahead: the 3-chunk window leaves no registers for more). Four chunks
-    // per lane (rows of 769-1024) need 10-wave blocks for the LDS and spill at their 168-VGPR budget: 358 vs 668
-    // Gcells/s for the column kernel at 813x407x407 (profiles/r2/r2_ragged_shapes.log); 8-wave blocks (2 waves per
-    // SIMD, 200 VGPRs, 4 output rows of 8) 597 vs 668 (r2_ragged_h4_8waves.log). Not instantiated.
-    if ((tune.wrap & 1) && nx > 256 && nx <= 768) {
-      if (nx <= 512)
-        done = jac ? apply_x2row_t<0, 1, 2, true>(dom, qi, region, sph, stream, tune)
-                   : apply_x2row_t<1, 1, 2, true>(dom, qi, region, sph, stream, tune);
-      else
-        done = jac ? apply_x2row_t<0, 1, 3, true>(dom, qi, region, sph, stream, tune)
-                   : apply_x2row_t<1, 1, 3, true>(dom, qi, region, sph, stream, tune);
-      if (done) return;
-    }
-    // rows of 769-832 cells (the 4-GPU ladder's 813): three chunks per lane plus one tail cell per lane
-    if ((tune.wrap & 1) && nx > 768 && nx <= 832) {
-      done = jac ? apply_x2row_t<0, 1, 3, false, 12, true>(dom, qi, region, sph, stream, tune)
-                 : apply_x2row_t<1, 1, 3, false, 12, true>(dom, qi, region, sph, stream, tune);
-      if (done) return;
-    }
-    STENCIL_REQUIRE(!tune.publish, "boundary-plane publication needs the whole-row kernel");
-    // x a whole number of 512-cell columns from a 16-B aligned first cell: the 512-cell column kernel
-    if (nx % 512 == 0 && (rr.lo.x - dom.radius().x(-1)) % 4 == 0) {
-      // one plane of lookahead (two would spill the Jacobi instance; the row kernel shows no difference)
-      jac ? apply_x2col2_wrap<float, 0, 1>(dom, qi, region, sph, stream, tune)
-          : apply_x2col2_wrap<float, 1, 1>(dom, qi, region, sph, stream, tune);
-      return;
-    }
-  }
-  if (!f32 && tune.x2row && !tune.publish) {
-    // fp64: x a whole number of 256-cell columns (two 2-double chunks per lane) from a 16-B aligned first cell
-    const Rect3 rr(region.lo - dom.accessor_origin(), region.hi - dom.accessor_origin());
-    const int64_t nx = rr.hi.x - rr.lo.x;
-    if (nx % 256 == 0 && (rr.lo.x - dom.radius().x(-1)) % 2 == 0) {
-      jac ? apply_x2col2_wrap<double, 0, 1>(dom, qi, region, sph, stream, tune)
-          : apply_x2col2_wrap<double, 1, 1>(dom, qi, region, sph, stream, tune);
-      return;
-    }
-  }
-  STENCIL_REQUIRE(!tune.publish, "boundary-plane publication needs the whole-row kernel");
-  // the column kernels wrap x only for whole chunks (ragged periodic rows are the whole-row kernel's)
-  STENCIL_REQUIRE(!(tune.wrap & 1) || (stencil7x2_wrappable_axes(dom, qi, 0) & 1),
-                  "in-kernel x wrap of a ragged row needs the whole-row kernel (fp32, x2row, 256 < nx < 1024)");
-  // one-chunk column kernel: 12 waves (one src row each, 8 output rows) and one plane of z lookahead, the measured best
-  // (bench.py 12x3 883-888, 12x1 881-883, 16x2 797-804, 8x2 759-772 Gcells/s, profiles/r1s4_bench_block_shapes.txt;
-  // the other shapes were removed in r6)
-  if (f32)
-    jac ? apply_x2_t<float, 0, 12, 1>(dom, qi, region, sph, stream, tune)
-        : apply_x2_t<float, 1, 12, 1>(dom, qi, region, sph, stream, tune);
-  else
-    jac ? apply_x2_t<double, 0, 12, 1>(dom, qi, region, sph, stream, tune)
-        : apply_x2_t<double, 1, 12, 1>(dom, qi, region, sph, stream, tune);
+  x2_run(dom, qi, region, kind, sph, stream, tune, nullptr);
+}
+
+X2LaunchInfo stencil7x2_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind,
+                                    const Spheres &sph, const StencilTune &tune) {
+  X2LaunchInfo info;
+  x2_run(dom, qi, region, kind, sph, nullptr, tune, &info);
+  return info;
+}
+
+bool stencil7x2_row_kernel_used(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StencilTune &tune) {
+  if (region.empty() || !stencil7x2_supported(dom, qi)) return false;
+  const Dim3 org = dom.accessor_origin();
+  return x2_row_form(stencil7x2_form(dom.elem_size(qi), region.hi.x - region.lo.x,
+                                     region.lo.x - org.x - dom.radius().x(-1), tune.wrap, tune.x2row, false,
+                                     dom.buffer_bytes(qi)));
 }
 
 template <typename T, int KIND>
@@ -1491,12 +1405,10 @@ static void apply_x2_regions_t(const LocalDomain &dom, int64_t qi, const std::ve
 void stencil7x2_apply_regions(const LocalDomain &dom, int64_t qi, const std::vector<Rect3> &regions, StencilKind kind,
                               const Spheres &sph, hipStream_t stream, int wrap) {
   STENCIL_REQUIRE(stencil7x2_supported(dom, qi), "two-step stencil needs a device fp32/fp64 quantity with depth-2 halos");
-  const Rect3 cr = dom.get_compute_region();
   std::vector<Rect3> rs;
   for (const auto &r : regions) {
     if (r.empty()) continue;
-    STENCIL_REQUIRE(cr.contains(r.lo) && r.hi.x <= cr.hi.x && r.hi.y <= cr.hi.y && r.hi.z <= cr.hi.z,
-                    "stencil region " << r << " outside compute region " << cr);
+    require_region_in_compute(dom, r);
     rs.push_back(r);
   }
   if (rs.empty()) return;
@@ -1573,8 +1485,7 @@ void stencil7x2_apply_exterior(const LocalDomain &dom, int64_t qi, const Rect3 &
     return;
   }
   STENCIL_REQUIRE(stencil7x2_supported(dom, qi), "two-step stencil needs a device fp32/fp64 quantity with depth-2 halos");
-  STENCIL_REQUIRE(c.contains(in.lo) && in.hi.x <= c.hi.x && in.hi.y <= c.hi.y && in.hi.z <= c.hi.z,
-                  "interior " << in << " outside compute region " << c);
+  require_region_in_compute(dom, in, "interior");
   // a wrapped axis is never cut by the interior: no slab is thin along it (x slabs load unwrapped row windows)
   check_wrap(dom, qi, in, tune.wrap, tune.x2row);
   const Dim3 lo = in.lo - c.lo, hi = c.hi - in.hi;

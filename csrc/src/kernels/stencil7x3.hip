@@ -913,22 +913,6 @@ template <typename T, int KIND> static X3XhKernel<T, KIND> x3_xh_kernel_ptr(bool
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static int64_t x3_resident_blocks(const void *kernel, int threads) {
-  static std::map<const void *, int64_t> cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(kernel);
-  if (it != cache.end()) return it->second;
-  int dev = 0, perCU = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, 0) != hipSuccess || perCU <= 0) perCU = 1;
-  (void)hipGetLastError();
-  const int64_t r = int64_t(perCU) * cus;
-  cache[kernel] = r;
-  return r;
-}
-
 // per-device sink for the stores of rows past a region's y end (2 chunks x 64 lanes x 16 B); allocated by
 // stencil7x3_supported (model init), never inside a stream capture
 static std::map<int, char *> gX3Sinks;
@@ -985,10 +969,7 @@ bool stencil7x3_supported(const LocalDomain &dom, int64_t qi, const Rect3 &regio
   if (dom.pitch(qi).x * dom.pitch(qi).y * es >= (int64_t(1) << 31)) return false;
   if ((wrapm & 1) && dom.buffer_bytes(qi) >= (int64_t(1) << 32) - 4096) return false;
   (void)x3_sink(dom.gpu(), true);
-  const int64_t lox = rad.x(-1);
-  return (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.curr_data(qi)) + lox * es) % 16 == 0) &&
-         (reinterpret_cast<uintptr_t>(static_cast<const char *>(dom.next_data(qi)) + lox * es) % 16 == 0) &&
-         (dom.pitch(qi).x * es) % 16 == 0;
+  return aligned_vector_layout(dom, qi, rad.x(-1));
 }
 
 // the launch schedule of a triple sweep over cols row groups (columns) of nz planes with `slots` resident blocks
@@ -1148,12 +1129,9 @@ static X3Launch<T> x3_prepare(const LocalDomain &dom, int64_t qi, const Rect3 &r
   const bool big = dom.buffer_bytes(qi) >= (int64_t(1) << 32) - 4096;
   const void *kern = XH ? (const void *)x3_xh_kernel_ptr<T, KIND>(big, false, rag) : x3_wrap_kernel_ptr<T, KIND>();
   const int64_t cols = int64_t(a.gx) * a.gy;
-  const int64_t resident = x3_resident_blocks(kern, 64 * NW);
+  const int64_t resident = resident_blocks(kern, 64 * NW, 1);
   // CUs left to the transport kernels running beside the sweep (pipelined triples: the gated exchange)
-  int cus = 256;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dom.gpu()) != hipSuccess) cus = 256;
-  const int64_t perCU = std::max<int64_t>(1, resident / std::max(1, cus));
-  const int64_t slots = std::max<int64_t>(perCU, resident - perCU * std::min(tune.reserveCUs, cus / 2));
+  const int64_t slots = launch_slots(resident, tune.reserveCUs, dom.gpu());
   if (tune.publish) {
     a.pub = reinterpret_cast<unsigned long long *>(tune.publish);
     a.pubLo = a.loz + tune.publishDepth;

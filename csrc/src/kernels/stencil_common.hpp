@@ -2,14 +2,17 @@
 
 #include <algorithm>
 #include <cmath>
+#include <map>
+#include <mutex>
 #include <vector>
-// Private device helpers shared by the 7-point stencil kernels (stencil7.hip, stencil7x2.hip).
+// Private device and host launch helpers shared by the stencil kernels (stencil7*.hip, stencil_star.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
+#include "stencil/rt/logging.hpp"
 
 namespace stencil {
 
@@ -162,6 +165,78 @@ inline StencilArgs<T> make_args(const LocalDomain &dom, int64_t qi, const Rect3 
   return a;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// host launch helpers: one copy for every stencil kernel file
+// ---------------------------------------------------------------------------------------------------------
+// what the launch paths ask the runtime once and then look up: resident blocks per kernel, CUs per device
+struct LaunchCache {
+  std::mutex mu;
+  std::map<const void *, int64_t> resident;
+  std::map<int, int> cus;
+  int cus_of(int dev) { // mu held; 256 (not cached) when the attribute query fails
+    auto it = cus.find(dev);
+    if (it != cus.end()) return it->second;
+    int n = 256;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
+    return cus[dev] = n;
+  }
+};
+inline LaunchCache &launch_cache() {
+  static LaunchCache c;
+  return c;
+}
+inline int device_cus(int dev) {
+  LaunchCache &c = launch_cache();
+  std::lock_guard<std::mutex> lk(c.mu);
+  return c.cus_of(dev);
+}
+// resident blocks of `kernel` over the whole (current) device, cached per kernel; fallbackPerCU where the occupancy
+// query fails
+inline int64_t resident_blocks(const void *kernel, int threads, int fallbackPerCU) {
+  LaunchCache &c = launch_cache();
+  std::lock_guard<std::mutex> lk(c.mu);
+  auto it = c.resident.find(kernel);
+  if (it != c.resident.end()) return it->second;
+  int dev = 0, perCU = 0;
+  (void)hipGetDevice(&dev);
+  const int cus = c.cus_of(dev);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, 0) != hipSuccess || perCU <= 0)
+    perCU = fallbackPerCU;
+  (void)hipGetLastError();
+  return c.resident[kernel] = int64_t(perCU) * cus;
+}
+// the resident blocks a launch on device `dev` may fill when it leaves reserveCUs CUs to the kernels of another stream
+inline int64_t launch_slots(int64_t resident, int reserveCUs, int dev) {
+  return slots_less_reserved(resident, reserveCUs, device_cus(dev));
+}
+
+// fp32 / fp64, or opaque 4- / 8-byte elements (computed on as fp32 / fp64); *es = the element size
+inline bool fp_quantity(const LocalDomain &dom, int64_t qi, int64_t *es) {
+  const DType dt = dom.dtype(qi);
+  *es = dom.elem_size(qi);
+  return dt == DType::F32 || dt == DType::F64 || (dt == DType::Bytes && (*es == 4 || *es == 8));
+}
+// the layout of the 16-B vector kernels: raw cell x0 of curr and of next starts a 16-B chunk in every row
+inline bool aligned_vector_layout(const LocalDomain &dom, int64_t qi, int64_t x0) {
+  const int64_t es = dom.elem_size(qi);
+  auto at16 = [&](const void *p) { return reinterpret_cast<uintptr_t>(static_cast<const char *>(p) + x0 * es) % 16 == 0; };
+  return at16(dom.curr_data(qi)) && at16(dom.next_data(qi)) && (dom.pitch(qi).x * es) % 16 == 0;
+}
+inline void require_region_in_compute(const LocalDomain &dom, const Rect3 &region, const char *what = "stencil region") {
+  const Rect3 cr = dom.get_compute_region();
+  STENCIL_REQUIRE(region.empty() || (cr.contains(region.lo) && region.hi.x <= cr.hi.x && region.hi.y <= cr.hi.y &&
+                                     region.hi.z <= cr.hi.z),
+                  what << " " << region << " outside compute region " << cr);
+}
+// along wrapped axes the region must be the whole compute region (the kernels wrap at its faces)
+inline void require_wrap_spans(const LocalDomain &dom, const Rect3 &region, int wrap) {
+  const Rect3 cr = dom.get_compute_region();
+  const int64_t lo[3] = {region.lo.x, region.lo.y, region.lo.z}, hi[3] = {region.hi.x, region.hi.y, region.hi.z};
+  const int64_t clo[3] = {cr.lo.x, cr.lo.y, cr.lo.z}, chi[3] = {cr.hi.x, cr.hi.y, cr.hi.z};
+  for (int ax = 0; ax < 3; ++ax)
+    STENCIL_REQUIRE(!((wrap >> ax) & 1) || (lo[ax] == clo[ax] && hi[ax] == chi[ax]),
+                    "region " << region << " does not span wrapped axis " << ax << " of " << cr);
+}
 
 // z-chunk length for a z-marching launch of `cols` block columns over nz planes with `resident` blocks resident
 // at once: maximise (useful planes / planes read) x (blocks / block slots of the rounds), i.e. balance the warm-up

@@ -282,26 +282,6 @@ template <typename T, int R> static void star_host(const StarArgs<T, R> &a) {
       }
 }
 
-// resident blocks of the fast kernel over the whole device (cached per kernel)
-static int64_t star_resident_blocks(const void *kernel, int threads) {
-  static std::map<const void *, int64_t> cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(kernel);
-  if (it != cache.end()) return it->second;
-  int dev = 0, perCU = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, 0) != hipSuccess || perCU <= 0) perCU = 2;
-  (void)hipGetLastError();
-  // at most two blocks per CU: the radius-1 fp32 kernel fits three, but 512^3 in 768 blocks ran 221 us against 212 us
-  // in 512 or 256 blocks (profiles/star/bench_stencil_starzc.csv); the other instances fit one or two anyway
-  perCU = std::min(perCU, kStarMaxBlocksPerCU);
-  const int64_t r = int64_t(perCU) * cus;
-  cache[kernel] = r;
-  return r;
-}
-
 // kernel arguments and the path apply takes for them; the fast path's grid is filled in (device sub-domains)
 template <typename T, int R>
 static StarArgs<T, R> star_plan(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StarWeights &wts,
@@ -336,8 +316,7 @@ static StarArgs<T, R> star_plan(const LocalDomain &dom, int64_t qi, const Rect3 
   const int off = ((a.lox - rxm) % V + V) % V;
   a.x0 = a.lox - off;
   a.nchunks = (a.hix - a.x0 + V - 1) / V;
-  const bool alignedLayout = (reinterpret_cast<uintptr_t>(a.src + a.x0) % 16 == 0) &&
-                             (reinterpret_cast<uintptr_t>(a.dst + a.x0) % 16 == 0) && ((a.px * int64_t(sizeof(T))) % 16 == 0);
+  const bool alignedLayout = aligned_vector_layout(dom, qi, a.x0);
   // the last chunk's vector load and the R cells right of it stay below the row's read limit; the R cells left of
   // chunk 0 are raw cells of the row (x0 >= the -x radius >= R)
   const bool fits = a.x0 + int64_t(a.nchunks) * V + R <= dom.row_limit(qi) && a.x0 >= R;
@@ -354,7 +333,11 @@ static StarArgs<T, R> star_plan(const LocalDomain &dom, int64_t qi, const Rect3 
     const void *kern = tune.nontemporal ? (const void *)stencil_star_kernel<T, R, kStarTY, kStarNW, true>
                                         : (const void *)stencil_star_kernel<T, R, kStarTY, kStarNW, false>;
     const int64_t cols = int64_t(a.gx) * a.gy;
-    const int64_t nzc = std::max<int64_t>(1, star_resident_blocks(kern, 64 * kStarNW) / cols);
+    // at most two blocks per CU: the radius-1 fp32 kernel fits three, but 512^3 in 768 blocks ran 221 us against 212 us
+    // in 512 or 256 blocks (profiles/star/bench_stencil_starzc.csv); the other instances fit one or two anyway
+    const int64_t resident = std::min(resident_blocks(kern, 64 * kStarNW, 2),
+                                      int64_t(kStarMaxBlocksPerCU) * device_cus(dom.gpu()));
+    const int64_t nzc = std::max<int64_t>(1, resident / cols);
     zc = int(std::max<int64_t>(kStarMinZc, (nz + nzc - 1) / nzc));
   }
   a.zc = zc;
@@ -414,10 +397,7 @@ static bool star_check(const LocalDomain &dom, int64_t qi, const Rect3 &region, 
   STENCIL_REQUIRE(qi >= 0 && qi < dom.num_data() && star_fp(dom, qi, f64), "star stencils take fp32 / fp64 quantities");
   STENCIL_REQUIRE(star_radii_ok(dom, w.radius), "star stencil of radius " << w.radius << " needs face radii >= " << w.radius);
   STENCIL_REQUIRE(tune.wrap == 0, "star stencils read halos (no in-kernel wrap)");
-  const Rect3 cr = dom.get_compute_region();
-  STENCIL_REQUIRE(region.empty() || (cr.contains(region.lo) && region.hi.all_ge(region.lo) && region.hi.x <= cr.hi.x &&
-                                     region.hi.y <= cr.hi.y && region.hi.z <= cr.hi.z),
-                  "stencil region " << region << " outside compute region " << cr);
+  require_region_in_compute(dom, region);
   return !region.empty();
 }
 

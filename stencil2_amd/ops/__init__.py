@@ -13,6 +13,7 @@ from .kernels import (  # noqa: F401
     star_supported,
     stencil7_apply,
     stencil7x2_apply,
+    stencil7x2_launch_info,
     stencil7x2_supported,
     stencil7x3_apply,
     stencil7x3_launch_info,

@@ -26,6 +26,21 @@ def stencil7x2_apply(dd, di: int, q: int, region, kind=_C.StencilKind.Jacobi, sp
     _C.stencil7x2_apply(native, di, q, region, kind, spheres, stream, tune if tune is not None else _C.StencilTune())
 
 
+def stencil7x2_launch_info(dd, di: int, q: int, region=None, kind=_C.StencilKind.Jacobi, spheres: bool = True,
+                           tune=None) -> dict:
+    """What `stencil7x2_apply` would launch for these arguments (nothing is launched; the same refusals raise;
+    `region` defaults to the sub-domain's compute region): `form` ("row": whole 512-cell periodic rows, "ragged2" /
+    "ragged3": periodic rows of 257-511 / 513-768 cells, "tail": 769-832 cells, "col2": two-chunk columns, "column":
+    the one-chunk column kernel; `_C.stencil7x2_form`), `wrap_variant` (the kernel's in-kernel wrap: 0 none, 1 y / z,
+    2 x too), `cols` (block columns), `slots` (resident blocks: the occupancy query less the share of
+    `tune.reserveCUs`) and the schedule `seg` (0 fixed z chunks, 1 balanced split, 2 lockstep parts plus second
+    segments, 3 lockstep rounds), `parts`, `rounds`, `blocks`, `zchunk`, `gz` (`_C.stencil7x2_schedule`)."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return _C.stencil7x2_launch_info(native, di, q, region, kind, spheres, tune if tune is not None else _C.StencilTune())
+
+
 def stencil7x3_supported(dd, di: int, q: int, tune=None) -> bool:
     """True when the fused three-step kernel can sweep quantity q of local sub-domain di: a device fp32/fp64 quantity
     in the aligned row layout with at least 3 x 3 x 16 cells, face radii >= 3 (edges and corners >= 1) on every axis

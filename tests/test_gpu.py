@@ -27,6 +27,18 @@ def _dd(st, size, radius, gpus, methods, dtype=torch.int64, transport=None):
     return dd, q
 
 
+def _x2_info(st, m, kind, **tune):
+    """What a fused pair of model m launches on sub-domain 0 (ops.stencil7x2_launch_info with the model's wrap axes)."""
+    from stencil2_amd.ops import stencil7x2_launch_info
+    t = st.StencilTune()
+    for k, v in tune.items():
+        setattr(t, k, v)
+    t.wrap = m.wrap_axes()
+    jac = kind == "jacobi"
+    return stencil7x2_launch_info(m.domain, 0, 0, kind=st.StencilKind.Jacobi if jac else st.StencilKind.Astaroth,
+                                  spheres=jac, tune=t)
+
+
 def _radii(st):
     a = st.Radius.constant(0)
     a.set_dir(1, 0, 0, 2)
@@ -481,6 +493,11 @@ def test_temporal2_whole_row_kernel(st, kind, size, gpus):
         m.init()
         assert m.temporal_blocking()
     assert ms[0].wrap_axes() & 1 and bool(ms[1].wrap_axes() & 1) == (size[0] % 4 == 0)
+    # the launch report names the row form the width implies (x stays whole in every sub-domain); x2row = 0: the column kernel
+    nx = size[0]
+    want = "row" if nx == 512 else "ragged2" if nx < 512 else "ragged3" if nx <= 768 else "tail"
+    for m, (r, early) in zip(ms, ((row, False), (0, False), (row, True))):
+        assert _x2_info(st, m, kind, x2row=r, x2early=early)["form"] == (want if r else "column")
     u = _gather(ms[0])
     for n in (5, 16):
         for m in ms:
@@ -558,6 +575,8 @@ def test_temporal2_col512_kernel(st, kind, size, gpus, wrap, cost, fp64):
     for m in ms:
         m.init()
         assert m.temporal_blocking()
+    for m, (row, early) in zip(ms, ((1, False), (0, False), (1, True))):
+        assert _x2_info(st, m, kind, x2row=row, x2early=early)["form"] == ("col2" if row else "column")
     u = _gather(ms[0])
     for n in (5, 16):
         for m in ms:
@@ -806,11 +825,26 @@ def test_temporal2_row_kernel_lockstep_parts(st, size, fp64):
     (40 columns: P = 6 over 240 blocks; 25 ragged 645-cell columns: P = 10; 17 tail-row columns: P = 15 over 255;
     the 512-cell column kernel over 2 x 16 columns: P = 8); grids of more row groups than blocks march rounds of
     whole columns (264 row groups: 2 rounds; 4 x 130 fp32 512-cell / fp64 256-cell columns: 3 rounds): bitwise equal
-    to single steps."""
+    to single steps. The launch report (ops.stencil7x2_launch_info) shows that schedule: x2_lockstep_schedule's for the
+    device's slots, and on 256 slots the figures above."""
+    from stencil2_amd import _C
     from stencil2_amd.ops import astaroth_step_reference
     m = st.AstarothSim(size, quantities=1, gpus=[0], temporal=2, axis_cost=(64, 3, 2), fp64=fp64)
     m.init()
     assert m.temporal_blocking()
+    info = _x2_info(st, m, "astaroth")
+    got = (info["seg"], info["parts"], info["blocks"], info["rounds"])
+    parts, blocks, rounds = _C.x2_lockstep_schedule(info["slots"], info["cols"], size[2])
+    if parts > 0:
+        assert got == (3 if rounds > 1 else 2, parts, blocks, rounds), info
+    else:  # a device whose slots admit no lockstep parts here: the balanced split
+        assert got == (1, 0, max(1, min(info["slots"], info["cols"] * size[2] // 16)), 1), info
+    if info["slots"] == 256:
+        assert (info["cols"],) + got == {(512, 320, 112): (40, 2, 6, 240, 1), (645, 200, 160): (25, 2, 10, 250, 1),
+                                         (813, 136, 256): (17, 2, 15, 255, 1), (1024, 128, 128): (32, 2, 8, 256, 1),
+                                         (512, 560, 112): (70, 3, 7, 245, 2), (512, 648, 240): (81, 2, 4, 256, 1),
+                                         (512, 2112, 16): (264, 3, 1, 132, 2), (2048, 1040, 16): (520, 3, 1, 174, 3),
+                                         (1024, 1040, 16): (520, 3, 1, 174, 3)}[size], info
     u = _gather(m)
     for n in (2, 6):
         m.run(n)
@@ -1372,8 +1406,8 @@ def test_x_face_lines_auto_device(st, rname, gpus, size):
 def test_ops_stencil7x2_apply_on_a_domain(st, kind, fp64):
     """ops.stencil7x2_apply on a user's DistributedDomain: exchange the depth-2 halos, one fused call = two steps of
     the torch oracle, bitwise; the same with the periodic image read in-kernel (tune.wrap = 7, no exchange)"""
-    from stencil2_amd.ops import astaroth_step_reference, stencil7x2_apply, stencil7x2_supported
-    K = st.StencilKind.Jacobi if kind == "jacobi" else st.StencilKind.Astaroth
+    from stencil2_amd.ops import astaroth_step_reference, stencil7x2_apply, stencil7x2_launch_info, stencil7x2_supported
+    K =st.StencilKind.Jacobi if kind == "jacobi" else st.StencilKind.Astaroth
     ref = jacobi_step_reference if kind == "jacobi" else astaroth_step_reference
     dtype = torch.float64 if fp64 else torch.float32
     L = (64, 48, 40)
@@ -1391,6 +1425,8 @@ def test_ops_stencil7x2_apply_on_a_domain(st, kind, fp64):
             dd.exchange()
         t = st.StencilTune()
         t.wrap = wrap
+        info = stencil7x2_launch_info(dd, 0, q, kind=K, spheres=kind == "jacobi", tune=t)
+        assert info["form"] == "column" and info["wrap_variant"] == (2 if wrap else 0), info  # 64-cell rows
         stencil7x2_apply(dd, 0, q, dd.domain(0).get_compute_region(), K, spheres=kind == "jacobi", tune=t)
         torch.cuda.synchronize()
         dd.swap()

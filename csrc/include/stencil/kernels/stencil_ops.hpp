@@ -188,6 +188,8 @@ void stencil7x2_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, S
 // 512, fp64 of 256; faces, edges and corners exchanged); y / z wrap in-kernel or read 3-deep halos.
 // Returns false (nothing launched) when this layout / region / tune is not supported.
 bool stencil7x3_supported(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StencilTune &tune);
+// cells per column of the form that reads x from halos (XH): two 16-B chunks per lane, 512 fp32 / 256 fp64
+int64_t stencil7x3_column_cells(int64_t elemSize);
 bool stencil7x3_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, StencilKind kind, const Spheres &sph,
                       hipStream_t stream, const StencilTune &tune);
 // S o S on several small regions (the exterior slabs of an overlapped fused pair), one thread per cell

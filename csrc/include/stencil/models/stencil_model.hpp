@@ -2,11 +2,16 @@
 // Iterated 7-point stencil applications on a DistributedDomain: the Jacobi3D and Astaroth-proxy "models".
 // Reference apps: bin/jacobi3d.cu:89-385 (hot loop :265-346) and bin/astaroth_sim.cu:150-284.
 //
-// One step() (overlap mode) is fully stream-ordered, no host synchronisation:
-//   compute[d]: interior(curr -> next)                               (overlaps the exchange)
-//   comm[dev] : exchange(curr halos) after ready[d] of the previous step -> exterior slabs(curr -> next)
-//   compute[d]: wait(exterior done) -> record ready
-//   host      : swap curr/next pointers
+// step() and run() are stream-ordered, no host synchronisation. init() decides once what a sweep enqueues:
+//   whole region: exchange(curr halos) -> sweep(curr -> next) of every sub-domain, as single steps or fused pairs /
+//                 triples of steps (temporal = 2 / 3); one device sub-domain runs all of it on one stream, as hipGraphs
+//   overlapped  : compute[d]: interior(curr -> next)                               (overlaps the exchange)
+//                 comm[dev] : exchange(curr halos) after ready[d] of the previous step -> exterior slabs(curr -> next)
+//                 compute[d]: wait(exterior done) -> record ready     (single steps and pairs: set_overlap_mode 1 / 2)
+//   pipelined   : whole-region pairs / triples publish their boundary planes early; the next exchange, gated on them,
+//                 runs beside the rest of the sweep (set_overlap_mode 3 / 4)
+//   forwarding  : the stencil kernels store their boundary outputs into the neighbours' halos; no exchange runs
+//   host        : swap curr/next pointers
 // The reference instead host-synchronises every compute stream each iteration (jacobi3d.cu:331-337).
 #include <map>
 #include <memory>
@@ -177,7 +182,31 @@ private:
   std::vector<Event> stepDone_;                                    // forwarding with several sub-domains
   hipGraphExec_t graphExec_[2] = {nullptr, nullptr};
   hipGraphExec_t graphBlock_[2] = {nullptr, nullptr}; // kGraphSteps steps starting at parity p
-  void enqueue_step(int k = 1); // k = 1: one step; k = 2: a fused pair (temporal blocking)
+  // init() in stages, in this order: each reads the config, the realized domain and what earlier stages decided
+  void decide_overlap_and_forwarding();
+  void decide_pairs();
+  void decide_pair_overlap(const std::vector<Rect3> &li); // li: get_local_interior(2)
+  bool triples_read_x_from_halos(int w) const;
+  bool decide_pair_wrap(); // true: overlapped and whole-region pairs wrap the same axes
+  void decide_toggle_and_pipelining(const std::vector<Rect3> &li, bool sameWrap);
+  void plan_single_steps();
+  void decide_triples();
+  void start(); // streams, initial condition, first forwarding exchange
+  bool on_device() const { return !dd_->domains().empty() && dd_->domains()[0].backend() == Backend::Device; }
+  bool only_same_gpu_copies() const { // every halo travels by the Kernel method
+    return dd_->exchange_bytes_for_method(MethodFlags::Kernel) == dd_->exchange_bytes_for_method(MethodFlags::All);
+  }
+  bool has_remote_halo(const std::vector<Rect3> &li) const; // some local interior differs from its compute region
+  // one sweep of k = 1 / 2 / 3 fused steps (a single step, a fused pair, a fused triple) and the exchange it needs
+  void enqueue_step(int k = 1);
+  void advance(int k); // enqueue_step(k), swap, record_ready where the streams need it, steps_ += k
+  void sweep(int k, size_t di, const Rect3 &region, hipStream_t s, const StencilTune &tune);
+  void whole_sweep(int k);
+  void pipelined_sweep(int k, bool gateOk);
+  void pair_slabs(size_t di, hipStream_t s);
+  void step_slabs(size_t di, const std::vector<Rect3> &slabs, hipStream_t s, const StencilTune &tune);
+  template <typename Slabs> void slabs_on_comm_stream(Slabs &&slabs);
+  template <typename Enqueue> hipGraphExec_t capture(Enqueue &&enqueue);
   void capture_block();         // graphBlock_[current parity] (no work is run)
   struct RunGraph {
     hipGraphExec_t exec = nullptr;
@@ -185,9 +214,14 @@ private:
   };
   std::map<std::pair<int, int>, RunGraph> runGraph_; // (steps, starting parity) -> a whole run(steps)
   void capture_run(int n);                           // runGraph_[{n, current parity}] (no work is run)
-  void drop_graphs();
-  bool pair_ok() const { return pairs_; }
+  hipError_t destroy_graphs(); // every recorded graph; the first error
   int64_t steps_ = 0;
 };
+
+// the axes (mask 1 = x, 2 = y, 4 = z) along which `swept` spans `compute` from end to end
+int spanned_axes(const Rect3 &compute, const Rect3 &swept);
+// both spheres keep c - radius >= lo and c + radius <= L - hi along every axis of the L-cell periodic grid:
+// (1, 2) for fused pairs and (2, 3) for triples, whose intermediate steps test halo cells at unwrapped coordinates
+bool spheres_clear_of_faces(const Spheres &sph, const Dim3 &L, int64_t lo, int64_t hi);
 
 } // namespace stencil

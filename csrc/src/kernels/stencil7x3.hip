@@ -931,7 +931,7 @@ static char *x3_sink(int dev, bool create) {
 }
 
 // the column width of the XH form: two 16-B chunks per lane
-static int64_t x3_column_cells(int64_t elemSize) { return 2 * 64 * (16 / elemSize); }
+int64_t stencil7x3_column_cells(int64_t elemSize) { return 2 * 64 * (16 / elemSize); }
 
 bool stencil7x3_supported(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StencilTune &tune) {
   if (dom.backend() != Backend::Device) return false;
@@ -949,7 +949,7 @@ bool stencil7x3_supported(const LocalDomain &dom, int64_t qi, const Rect3 &regio
     // x from 3-deep halos, in columns of CW cells; a ragged row's last column holds r = n.x mod CW cells and reads
     // the 3 halo cells beyond them inside its own chunks, so r <= CW - 3 (r = CW - 2, CW - 1 would need the right
     // edge wave's machinery at the ragged end: such rows keep the fused pairs)
-    const int64_t cw = x3_column_cells(es);
+    const int64_t cw = stencil7x3_column_cells(es);
     if (rad.x(-1) < 3 || rad.x(1) < 3 || n.x < 3 || n.x % cw > cw - 3) return false;
   }
   if (!(wrapm & 2) && (rad.y(-1) < 3 || rad.y(1) < 3)) return false;
@@ -1121,7 +1121,7 @@ static X3Launch<T> x3_prepare(const LocalDomain &dom, int64_t qi, const Rect3 &r
   a.sphr = int(sph.radius);
   const int nx = a.hix - a.lox, ny = a.hiy - a.loy, nz = a.hiz - a.loz;
   // XH: columns of CW cells; a ragged row's last column holds xr < CW of them (the schedule treats it as a whole one)
-  const int cw = int(x3_column_cells(int64_t(sizeof(T))));
+  const int cw = int(stencil7x3_column_cells(int64_t(sizeof(T))));
   a.gx = XH ? (nx + cw - 1) / cw : 1;
   a.xr = XH ? nx - (a.gx - 1) * cw : nx;
   const bool rag = XH && a.xr < cw;

@@ -16,6 +16,7 @@
 #include "stencil/core/boundary.hpp"
 #include "stencil/domain/distributed_domain.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
+#include "stencil/models/stencil_model.hpp"
 #include "stencil/rt/stream.hpp"
 #include "stencil/rt/allocator.hpp"
 #include "stencil/rt/build_info.hpp"
@@ -372,6 +373,32 @@ static void check_x2_split(StencilKind kind) {
 }
 TEST(gpu_x2_split_regions_jacobi, true) { check_x2_split(StencilKind::Jacobi); }
 TEST(gpu_x2_split_regions_astaroth, true) { check_x2_split(StencilKind::Astaroth); }
+
+// the pure helpers of StencilModel::init()
+TEST(model_decision_helpers, false) {
+  const Rect3 c(Dim3(0, 0, 0), Dim3(16, 12, 10));
+  CHECK(spanned_axes(c, c) == 7);
+  CHECK(spanned_axes(c, Rect3(Dim3(0, 0, 2), Dim3(16, 12, 8))) == 3);
+  CHECK(spanned_axes(c, Rect3(Dim3(0, 1, 0), Dim3(16, 12, 10))) == 5);
+  CHECK(spanned_axes(c, Rect3(Dim3(0, 0, 0), Dim3(15, 12, 9))) == 2);
+  CHECK(spanned_axes(c, Rect3(Dim3(1, 1, 1), Dim3(15, 11, 9))) == 0);
+  Spheres s;
+  s.enabled = true;
+  s.radius = 3;
+  s.hot = Dim3(10, 5, 5);
+  s.cold = Dim3(20, 5, 5);
+  // y and z: 5 - 3 = 2 and 5 + 3 = 8, so triples need L >= 11 and pairs L >= 10; x: 20 + 3 = 23
+  CHECK(spheres_clear_of_faces(s, Dim3(30, 11, 11), 1, 2) && spheres_clear_of_faces(s, Dim3(30, 11, 11), 2, 3));
+  CHECK(spheres_clear_of_faces(s, Dim3(30, 10, 11), 1, 2) && !spheres_clear_of_faces(s, Dim3(30, 10, 11), 2, 3));
+  CHECK(!spheres_clear_of_faces(s, Dim3(30, 11, 9), 1, 2));
+  CHECK(spheres_clear_of_faces(s, Dim3(25, 11, 11), 1, 2) && !spheres_clear_of_faces(s, Dim3(25, 11, 11), 2, 3));
+  CHECK(!spheres_clear_of_faces(s, Dim3(24, 11, 11), 1, 2));
+  s.hot = Dim3(10, 4, 5); // 4 - 3 = 1: the pairs' lower margin holds, the triples' does not
+  CHECK(spheres_clear_of_faces(s, Dim3(30, 11, 11), 1, 2) && !spheres_clear_of_faces(s, Dim3(30, 11, 11), 2, 3));
+  s.hot = Dim3(10, 3, 5);
+  CHECK(!spheres_clear_of_faces(s, Dim3(30, 11, 11), 1, 2));
+  CHECK(stencil7x3_column_cells(4) == 512 && stencil7x3_column_cells(8) == 256);
+}
 
 TEST(transport_options_defaults, false) {
   TransportOptions o;

@@ -104,7 +104,9 @@ class StencilModel:
     def set_overlap_mode(self, mode: int):
         """0 = whole-region pairs; 1 = overlapped, slabs on the comm stream beside the interior sweep; 2 = overlapped,
         slabs after the interior sweep on the compute stream; 3 = pipelined (can_pipeline()): whole-region sweeps that
-        publish their boundary z planes, the next pair's exchange gated on them runs beside the rest of the sweep."""
+        publish their boundary z planes, the next pair's exchange gated on them runs beside the rest of the sweep;
+        4 = the same pipelining for fused triples (can_pipeline_triples()), each depth-3 exchange gated on the previous
+        triple's boundary planes."""
         self._m.set_overlap_mode(int(mode))
 
     def can_pipeline(self) -> bool:
@@ -140,7 +142,9 @@ class StencilModel:
         return self._m.temporal_blocking()
 
     def temporal_triples(self) -> bool:
-        """True when run() advances in fused triples of steps (stencil7x3, temporal=3 on one fully periodic GPU)."""
+        """True when run() advances in fused triples of steps (stencil7x3, one depth-3 exchange per triple): temporal=3,
+        device sub-domains of 512-cell fp32 rows wrapped in-kernel or of 512-cell fp32 / 256-cell fp64 columns whose x
+        halos come from the exchange (the last column may be partial), and whole-region sweeps (not overlapped)."""
         return self._m.temporal_triples()
 
     def wrap_axes(self) -> int:

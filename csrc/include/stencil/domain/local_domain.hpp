@@ -166,6 +166,10 @@ public:
   std::vector<unsigned char> quantity_to_host(int64_t qi) const { return region_to_host(Dim3(0, 0, 0), raw_size(), qi); }
   // fill every byte of both buffers of quantity qi (e.g. NaN poisoning for race canaries)
   void fill_bytes(int64_t qi, uint8_t v, bool curr, bool next);
+  // every byte fill_bytes fills of one buffer (curr or next): all buffer_bytes(qi) bytes from the front padding of the
+  // first row on (raw [0,0,0] sits pad_x(qi) elements in), row padding included, plus the tail allocated behind the
+  // last row with shared halo lines. With fill_bytes a test sees every byte a kernel could have stored to.
+  std::vector<unsigned char> buffer_to_host(int64_t qi, bool curr = true) const;
 
   void set_device() const;
 

@@ -515,6 +515,12 @@ PYBIND11_MODULE(_C, m) {
         auto v = d.quantity_to_host(q);
         return py::bytes(reinterpret_cast<const char *>(v.data()), v.size());
       })
+      .def("buffer_to_host",
+           [](const LocalDomain &d, int64_t q, bool curr) {
+             auto v = d.buffer_to_host(q, curr);
+             return py::bytes(reinterpret_cast<const char *>(v.data()), v.size());
+           },
+           py::arg("qi"), py::arg("curr") = true)
       .def("fill_bytes", &LocalDomain::fill_bytes);
 
   // ---------------- DistributedDomain ----------------
@@ -714,12 +720,50 @@ PYBIND11_MODULE(_C, m) {
   // ---------------- kernels ----------------
   m.def("stencil7_apply",
         [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &region, StencilKind kind, bool spheres,
-           uintptr_t stream) {
+           uintptr_t stream, const py::object &tune) {
           const Spheres s = spheres ? Spheres::jacobi(dd.get_compute_region()) : Spheres();
-          stencil7_apply(dd.domains().at(di), q, region, kind, s, reinterpret_cast<hipStream_t>(stream));
+          stencil7_apply(dd.domains().at(di), q, region, kind, s, reinterpret_cast<hipStream_t>(stream),
+                         tune.is_none() ? StencilTune() : tune.cast<StencilTune>());
         },
         py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("kind"), py::arg("spheres"),
-        py::arg("stream") = 0);
+        py::arg("stream") = 0, py::arg("tune") = py::none());
+  m.def("stencil7_apply_regions",
+        [](DistributedDomain &dd, size_t di, int64_t q, const std::vector<Rect3> &regions, StencilKind kind,
+           bool spheres, uintptr_t stream, const py::object &tune) {
+          // one single step on several regions in one call (the exterior slabs of an overlapped step)
+          const Spheres s = spheres ? Spheres::jacobi(dd.get_compute_region()) : Spheres();
+          stencil7_apply_regions(dd.domains().at(di), q, regions, kind, s, reinterpret_cast<hipStream_t>(stream),
+                                 tune.is_none() ? StencilTune() : tune.cast<StencilTune>());
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("regions"), py::arg("kind"), py::arg("spheres"),
+        py::arg("stream") = 0, py::arg("tune") = py::none());
+  m.def("stencil7_wrappable_axes",
+        [](DistributedDomain &dd, size_t di, int64_t q) { return stencil7_wrappable_axes(dd.domains().at(di), q); },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"));
+  m.def("stencil7x2_wrappable_axes",
+        [](DistributedDomain &dd, size_t di, int64_t q, int x2row) {
+          return stencil7x2_wrappable_axes(dd.domains().at(di), q, x2row);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("x2row") = 1);
+  m.def("stencil7x2_apply_regions",
+        [](DistributedDomain &dd, size_t di, int64_t q, const std::vector<Rect3> &regions, StencilKind kind,
+           bool spheres, uintptr_t stream, int wrap) {
+          // two fused steps on several small regions, one thread per cell
+          const Spheres s = spheres ? Spheres::jacobi(dd.get_compute_region()) : Spheres();
+          stencil7x2_apply_regions(dd.domains().at(di), q, regions, kind, s, reinterpret_cast<hipStream_t>(stream), wrap);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("regions"), py::arg("kind"), py::arg("spheres"),
+        py::arg("stream") = 0, py::arg("wrap") = 0);
+  m.def("stencil7x2_apply_exterior",
+        [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &interior, StencilKind kind, bool spheres,
+           uintptr_t stream, const py::object &tune) {
+          // two fused steps on the compute region minus `interior`
+          const Spheres s = spheres ? Spheres::jacobi(dd.get_compute_region()) : Spheres();
+          stencil7x2_apply_exterior(dd.domains().at(di), q, interior, kind, s, reinterpret_cast<hipStream_t>(stream),
+                                    tune.is_none() ? StencilTune() : tune.cast<StencilTune>());
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("interior"), py::arg("kind"), py::arg("spheres"),
+        py::arg("stream") = 0, py::arg("tune") = py::none());
   m.def(
       "stencil7x3_apply",
       [](DistributedDomain &dd, size_t di, int64_t q, StencilKind kind, bool spheres, uintptr_t stream,

@@ -239,4 +239,20 @@ void LocalDomain::fill_bytes(int64_t qi, uint8_t v, bool curr, bool next) {
   }
 }
 
+std::vector<unsigned char> LocalDomain::buffer_to_host(int64_t qi, bool curr) const {
+  STENCIL_REQUIRE(realized_, "buffer_to_host before realize");
+  const int64_t bytes = buffer_bytes(qi) + tailX_.at(size_t(qi)) * elem_size(qi);
+  std::vector<unsigned char> out{};
+  out.resize(size_t(bytes));
+  const char *p = static_cast<const char *>(curr ? curr_data(qi) : next_data(qi)) - padX_[size_t(qi)] * elem_size(qi);
+  if (backend_ == Backend::Host) {
+    std::memcpy(out.data(), p, size_t(bytes));
+  } else {
+    set_device();
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out.data(), p, size_t(bytes), hipMemcpyDeviceToHost));
+  }
+  return out;
+}
+
 } // namespace stencil

@@ -12,7 +12,12 @@ from .kernels import (  # noqa: F401
     star_launch_info,
     star_supported,
     stencil7_apply,
+    stencil7_apply_regions,
+    stencil7_wrappable_axes,
     stencil7x2_apply,
+    stencil7x2_apply_exterior,
+    stencil7x2_apply_regions,
+    stencil7x2_wrappable_axes,
     stencil7x2_launch_info,
     stencil7x2_supported,
     stencil7x3_apply,

@@ -4,10 +4,51 @@ from __future__ import annotations
 from .. import _C
 
 
-def stencil7_apply(dd, di: int, q: int, region, kind=_C.StencilKind.Jacobi, spheres: bool = True, stream: int = 0):
-    """next(region) = 7-point stencil of curr for quantity q of local sub-domain di (HIP kernel on its GPU)."""
+def _tune(tune):
+    return tune if tune is not None else _C.StencilTune()
+
+
+def stencil7_apply(dd, di: int, q: int, region, kind=_C.StencilKind.Jacobi, spheres: bool = True, stream: int = 0,
+                   tune=None):
+    """next(region) = 7-point stencil of curr for quantity q of local sub-domain di (HIP kernel on its GPU). `tune`
+    (a StencilTune, default the default tune) selects the kernel instance: variant, ty, nw, zchunk, nontemporal,
+    xcd_remap, alternate_z, and wrap (the axes read periodically in-kernel: `stencil7_wrappable_axes`)."""
     native = getattr(dd, "native", dd)
-    _C.stencil7_apply(native, di, q, region, kind, spheres, stream)
+    _C.stencil7_apply(native, di, q, region, kind, spheres, stream, _tune(tune))
+
+
+def stencil7_wrappable_axes(dd, di: int, q: int) -> int:
+    """mask (1 = x, 2 = y, 4 = z) of the axes `stencil7_apply` / `stencil7_apply_regions` can wrap in-kernel"""
+    return _C.stencil7_wrappable_axes(getattr(dd, "native", dd), di, q)
+
+
+def stencil7_apply_regions(dd, di: int, q: int, regions, kind=_C.StencilKind.Jacobi, spheres: bool = True,
+                           stream: int = 0, tune=None):
+    """One single step on every region of `regions` (Rect3 in global coordinates, each inside the compute region) in
+    one call: the exterior slabs of an overlapped step. Of `tune` only `wrap` matters on the device."""
+    native = getattr(dd, "native", dd)
+    _C.stencil7_apply_regions(native, di, q, list(regions), kind, spheres, stream, _tune(tune))
+
+
+def stencil7x2_wrappable_axes(dd, di: int, q: int, x2row: int = 1) -> int:
+    """mask (1 = x, 2 = y, 4 = z) of the axes the fused-pair kernels can wrap in-kernel (x2row as StencilTune.x2row)"""
+    return _C.stencil7x2_wrappable_axes(getattr(dd, "native", dd), di, q, x2row)
+
+
+def stencil7x2_apply_regions(dd, di: int, q: int, regions, kind=_C.StencilKind.Jacobi, spheres: bool = True,
+                             stream: int = 0, wrap: int = 0):
+    """next = S(S(curr)) on every region of `regions`, one thread per cell (the thick exterior slabs of an overlapped
+    fused pair); `wrap`: the axes read periodically in-kernel."""
+    native = getattr(dd, "native", dd)
+    _C.stencil7x2_apply_regions(native, di, q, list(regions), kind, spheres, stream, wrap)
+
+
+def stencil7x2_apply_exterior(dd, di: int, q: int, interior, kind=_C.StencilKind.Jacobi, spheres: bool = True,
+                              stream: int = 0, tune=None):
+    """next = S(S(curr)) on the compute region minus `interior` (the exterior of an overlapped fused pair): slabs up to
+    4 cells thick by the thin-slab kernels, thicker ones one thread per cell."""
+    native = getattr(dd, "native", dd)
+    _C.stencil7x2_apply_exterior(native, di, q, interior, kind, spheres, stream, _tune(tune))
 
 
 def stencil7x2_supported(dd, di: int, q: int) -> bool:
@@ -72,10 +113,6 @@ def stencil7x3_apply(dd, di: int, q: int, kind=_C.StencilKind.Jacobi, spheres: b
     only cells of the compute region are written (csrc/src/kernels/stencil7x3.hip)."""
     native = getattr(dd, "native", dd)
     return _C.stencil7x3_apply(native, di, q, kind, spheres, stream, tune if tune is not None else _C.StencilTune())
-
-
-def _tune(tune):
-    return tune if tune is not None else _C.StencilTune()
 
 
 def star_supported(dd, di: int, q: int, weights) -> bool:

@@ -4,12 +4,15 @@
 // Prints CSV `kernel,variant,ty,zc,us,gcells,eff_TBps` where eff_TBps counts the 8 B/cell minimum traffic.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/domain/packer.hpp"
+#include "stencil/kernels/field_reduce.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/rt/argparse.hpp"
 #include "stencil/rt/stream.hpp"
@@ -58,7 +61,8 @@ int main(int argc, char **argv) {
   ArgParser p("7-point stencil kernel sweep on one GPU");
   p.option(&n, "--n", "cube edge").option(&iters, "--iters", "timed launches per config")
       .option(&reps, "--reps", "repetitions of the whole sweep (interleaved)")
-      .option(&only, "--only", "run only 'lds', 'reg', 'copy' or 'star' (weighted stars of radius 1-3 beside stencil7)");
+      .option(&only, "--only", "run only 'lds', 'reg', 'copy', 'star' (weighted stars of radius 1-3 beside stencil7) or 'reduce' (field "
+                             "reductions beside the single-step sweep)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -375,6 +379,53 @@ int main(int argc, char **argv) {
                     cells * 8 / us / 1e6, li.path);
       }
     }
+  }
+  if (only == "reduce") {
+    // Field reductions beside the default single-step sweep (stencil7_apply, default tune), all on the same field in
+    // one invocation. Every call is timed on its own, blocking (launch, then wait for the stream: a reduction's
+    // result is only of use on the host), interleaved sweep / one operand / two operands per round; the medians over
+    // reps x iters calls are compared: the one-operand reduction reads half the bytes the sweep moves and must not
+    // take longer than it. `stream_us` is the mean of iters back-to-back launches between two events.
+    ReduceScratch scratch;
+    StencilTune t;
+    auto blocking_us = [&](auto &&fn, std::vector<double> &out) {
+      const auto t0 = std::chrono::steady_clock::now();
+      fn();
+      HIP_CHECK(hipStreamSynchronize(s));
+      out.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    };
+    auto median = [](std::vector<double> v) {
+      std::sort(v.begin(), v.end());
+      return v.empty() ? 0.0 : (v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]));
+    };
+    auto sweep = [&] { stencil7_apply(ld, 0, reg, StencilKind::Jacobi, sph, s, t); };
+    auto red1 = [&] { field_reduce_enqueue(ld, 0, true, -1, false, reg, scratch, s); };
+    auto red2 = [&] { field_reduce_enqueue(ld, 0, true, 0, false, reg, scratch, s); };
+    const ReduceLaunchInfo li = field_reduce_launch_info(ld, 0, true, 0, false, reg);
+    for (int i = 0; i < 3; ++i) { // warm-up: first launches, scratch allocation
+      sweep();
+      red1();
+      red2();
+    }
+    s.sync();
+    std::vector<double> us7, us1, us2;
+    for (int rep = 0; rep < std::max(reps, 1); ++rep)
+      for (int i = 0; i < iters; ++i) {
+        blocking_us(sweep, us7);
+        blocking_us(red1, us1);
+        blocking_us(red2, us2);
+      }
+    const double m7 = median(us7), m1 = median(us1), m2 = median(us2);
+    const double s7 = timeit(sweep), s1 = timeit(red1), s2 = timeit(red2);
+    std::printf("kernel,operands,path,blocks,median_us,gcells,read_TBps,stream_us\n");
+    std::printf("stencil7,%d,%d,0,%.2f,%.1f,%.3f,%.2f\n", t.variant, t.ty, m7, cells / m7 / 1e3, cells * 4 / m7 / 1e6, s7);
+    std::printf("field_reduce,1,%d,%lld,%.2f,%.1f,%.3f,%.2f\n", li.path, (long long)li.blocks, m1, cells / m1 / 1e3,
+                cells * 4 / m1 / 1e6, s1);
+    std::printf("field_reduce,2,%d,%lld,%.2f,%.1f,%.3f,%.2f\n", li.path, (long long)li.blocks, m2, cells / m2 / 1e3,
+                cells * 8 / m2 / 1e6, s2);
+    const FieldStats r = scratch.result();
+    std::printf("reduce_check,count,%lld,nonfinite,%lld,sum_sq,%.17g\n", (long long)r.count, (long long)r.nonfinite, r.sum_sq);
+    std::printf("reduce_condition,one_operand_median_us,%.2f,sweep_median_us,%.2f,%s\n", m1, m7, m1 <= m7 ? "met" : "MISSED");
   }
   for (int rep = 0; rep < reps; ++rep)
   if (only == "x2pp") {

@@ -27,6 +27,7 @@
 #include "stencil/core/boundary.hpp"
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/domain/packer.hpp"
+#include "stencil/kernels/field_reduce.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/rt/stream.hpp"
 #include "stencil/topo/placement.hpp"
@@ -335,6 +336,17 @@ public:
   bool gated_send_supported(int skipAxes, bool withTranslate = false) const;
   void swap();
 
+  // ---- field reductions (stencil/kernels/field_reduce.hpp) ----
+  // FieldStats of quantity qa (curr or next), or of the difference and dot product of (qa, currA) and (qb, currB),
+  // over the compute region of the whole grid. Collective unless `local`. One reduction per local sub-domain is
+  // enqueued on its device's comm stream, ordered after the domain's compute and exchange work the way a blocking
+  // exchange() orders itself (record_ready events, else the null stream with nullStreamProducers, else a device
+  // synchronize); the sub-domains are merged in domain-index order, the ranks' structs allgathered and merged in rank
+  // order, so every rank returns identical bits. A poisoned domain refuses.
+  FieldStats reduce(int64_t qa, bool currA = true, int64_t qb = -1, bool currB = false, bool local = false);
+  // the reduction scratch (partial slab and pinned result) of local domain di
+  ReduceScratch &reduce_scratch(size_t di);
+
   // ---- transport log (wait vs copy of the fused co-located kernels) ----
   // keep the last `exchanges` exchanges' device timestamps (s_memrealtime, 100-MHz constant clock) of every fused
   // Colocated pack / unpack kernel: per exchange {send start, send after credit wait, send after copies, send
@@ -407,6 +419,7 @@ public:
 private:
   std::unique_ptr<Placement> placement_;
   std::vector<LocalDomain> domains_;
+  std::vector<std::unique_ptr<ReduceScratch>> reduceScratch_; // per local domain, allocated on first use
   std::vector<ExchangePlanEntry> plan_;
   std::vector<std::array<uint8_t, 27>> remoteHalo_; // per local domain, per halo side: filled by a non-Kernel method
   std::array<uint64_t, 5> bytesPerMethod_{}; // indexed by log2(method)

@@ -7,6 +7,10 @@
 
 #include <cstring>
 
+#include <cmath>
+#include <limits>
+#include <sstream>
+
 #include "stencil/comm/proc_group.hpp"
 #include "stencil/comm/ipc_event.hpp"
 #include "stencil/comm/rccl_comm.hpp"
@@ -602,7 +606,74 @@ PYBIND11_MODULE(_C, m) {
       .def_readonly("dir", &ExchangePlanEntry::dir)
       .def_readonly("bytes", &ExchangePlanEntry::bytes);
 
+  // ---------------- field reductions ----------------
+  py::class_<FieldStats>(m, "FieldStats")
+      .def(py::init<>())
+      .def_readonly("count", &FieldStats::count)
+      .def_readonly("nonfinite", &FieldStats::nonfinite)
+      .def_readonly("sum", &FieldStats::sum)
+      .def_readonly("sum_abs", &FieldStats::sum_abs)
+      .def_readonly("sum_sq", &FieldStats::sum_sq)
+      .def_readonly("min", &FieldStats::min)
+      .def_readonly("max", &FieldStats::max)
+      .def_readonly("dot", &FieldStats::dot)
+      .def_property_readonly("l1", [](const FieldStats &s) { return s.sum_abs; })
+      .def_property_readonly("l2", [](const FieldStats &s) { return std::sqrt(s.sum_sq); })
+      .def_property_readonly("linf",
+                             [](const FieldStats &s) {
+                               // nan when a cell is not finite, 0 for an empty region
+                               if (s.nonfinite > 0) return std::numeric_limits<double>::quiet_NaN();
+                               if (s.count == 0) return 0.0;
+                               return std::max(-s.min, s.max);
+                             })
+      .def("__repr__", [](const FieldStats &s) {
+        std::ostringstream o;
+        o << "FieldStats(count=" << s.count << ", nonfinite=" << s.nonfinite << ", sum=" << s.sum << ", sum_abs="
+          << s.sum_abs << ", sum_sq=" << s.sum_sq << ", min=" << s.min << ", max=" << s.max << ", dot=" << s.dot << ")";
+        return o.str();
+      });
+  m.def("field_reduce_supported",
+        [](DistributedDomain &dd, size_t di, int64_t qa, int64_t qb) {
+          return field_reduce_supported(dd.domains().at(di), qa, qb);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qa"), py::arg("qb") = -1);
+  m.def("field_reduce",
+        [](DistributedDomain &dd, size_t di, int64_t qa, bool currA, int64_t qb, bool currB, const Rect3 &region,
+           uintptr_t stream, int maxBlocks) {
+          // blocking; the scratch is the domain's own (one reduction in flight per sub-domain)
+          const LocalDomain &d = dd.domains().at(di);
+          return field_reduce(d, qa, currA, qb, currB, region, dd.reduce_scratch(di),
+                              reinterpret_cast<hipStream_t>(stream), maxBlocks);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qa"), py::arg("curr_a"), py::arg("qb"), py::arg("curr_b"),
+        py::arg("region"), py::arg("stream") = 0, py::arg("max_blocks") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def("field_reduce_launch_info",
+        [](DistributedDomain &dd, size_t di, int64_t qa, bool currA, int64_t qb, bool currB, const Rect3 &region,
+           int maxBlocks) {
+          // what field_reduce would run (nothing is launched)
+          const ReduceLaunchInfo r = field_reduce_launch_info(dd.domains().at(di), qa, currA, qb, currB, region, maxBlocks);
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["blocks"] = r.blocks;
+          o["items"] = r.items;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qa"), py::arg("curr_a"), py::arg("qb"), py::arg("curr_b"),
+        py::arg("region"), py::arg("max_blocks") = 0);
+
   py::class_<DistributedDomain, std::shared_ptr<DistributedDomain>>(m, "DistributedDomain")
+      .def("reduce",
+           [](DistributedDomain &d, int64_t q, py::object other, bool curr, bool otherCurr, bool local) {
+             const int64_t qb = other.is_none() ? -1 : other.cast<int64_t>();
+             STENCIL_REQUIRE(other.is_none() || qb >= 0, "reduce: other must be a quantity index or None");
+             py::gil_scoped_release r;
+             return d.reduce(q, curr, qb, otherCurr, local);
+           },
+           py::arg("q"), py::arg("other") = py::none(), py::arg("curr") = true, py::arg("other_curr") = false,
+           py::arg("local") = false,
+           "FieldStats of quantity q (curr or next buffer), or with `other` of the difference q - other and their dot "
+           "product, over the whole grid; collective unless local")
       .def(py::init([](int64_t x, int64_t y, int64_t z, std::shared_ptr<comm::ProcGroup> pg) {
              py::gil_scoped_release r;
              return std::make_shared<DistributedDomain>(x, y, z, pg);

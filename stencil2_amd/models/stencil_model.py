@@ -82,6 +82,24 @@ class StencilModel:
         in `runs` also a graph of a whole run(n), which run(n) then replays as one launch."""
         self._m.prepare(list(runs))
 
+    def run_until(self, tol: float, max_iters: int, check_every: int = 10, norm="inf"):
+        """Step until the change made by one step falls below `tol`: returns (iters_done, value). Advances in blocks of
+        `check_every` steps (run(check_every - 1), which may fuse pairs / triples, then one single step()),
+        synchronizes and evaluates the `norm` (1, 2 or "inf"; over every quantity) of curr - next over the compute
+        regions, the change made by the block's last single step; stops at the first check with value < tol, or at
+        `max_iters`. Raises FloatingPointError as soon as a check sees a non-finite cell. Collective: every rank
+        computes the same value. A single step leaves the previous state intact in the compute region of next in
+        every configuration (forwarding, overlapped, wrapped, temporal remainders: models/until.py), so none is
+        refused. The default check_every = 10 is a bytes estimate, not a measurement: the two-operand reduction reads
+        about as many bytes as one single step moves, so a check every tenth step costs on the order of a tenth of
+        single steps, and more than that beside fused triples ("Field reductions")."""
+        from .until import run_until
+        if self._dd is None:
+            raise RuntimeError("run_until before init()")
+        qs = range(self._dd.domain(0).num_data())
+        return run_until(self, lambda q: self._dd.reduce(q, other=q, other_curr=False), qs, tol, max_iters, check_every,
+                         norm)
+
     def synchronize(self):
         self._m.synchronize()
 

@@ -8,6 +8,9 @@ from .reference import (  # noqa: F401
     star_step_reference,
 )
 from .kernels import (  # noqa: F401
+    field_reduce,
+    field_reduce_launch_info,
+    field_reduce_supported,
     star_apply,
     star_launch_info,
     star_supported,

@@ -115,6 +115,41 @@ def stencil7x3_apply(dd, di: int, q: int, kind=_C.StencilKind.Jacobi, spheres: b
     return _C.stencil7x3_apply(native, di, q, kind, spheres, stream, tune if tune is not None else _C.StencilTune())
 
 
+def _reduce_args(dd, di, q, other, region):
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return native, (-1 if other is None else int(other)), region
+
+
+def field_reduce(dd, di: int, q: int, other=None, curr: bool = True, other_curr: bool = False, region=None,
+                 stream: int = 0, max_blocks: int = 0):
+    """FieldStats (count, nonfinite, sum, sum_abs, sum_sq, min, max, dot; l1, l2, linf) of quantity q of local
+    sub-domain di over `region` (global coordinates, default the sub-domain's compute region); no communication.
+    One operand: e = double(q); with `other`: e = double(q) - double(other) and dot = sum of q * other. `curr` /
+    `other_curr` pick each operand's curr or next buffer. Blocking: enqueued on `stream` and waited for. Accumulation
+    is in double, without atomics, in an order fixed by the layout, the region and the grid (`max_blocks`: 0 = one
+    round of resident blocks, else exactly that many), so the same call returns the same bits every time
+    (csrc/src/kernels/field_reduce.hip)."""
+    native, qb, region = _reduce_args(dd, di, q, other, region)
+    return _C.field_reduce(native, di, q, curr, qb, other_curr, region, stream, max_blocks)
+
+
+def field_reduce_launch_info(dd, di: int, q: int, other=None, curr: bool = True, other_curr: bool = False, region=None,
+                             max_blocks: int = 0) -> dict:
+    """What `field_reduce` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the row kernel of the aligned vector layout, "generic": one thread per cell, "host", "none": empty
+    region), `blocks` of the launch and `items`, the (row, plane) pairs of the region."""
+    native, qb, region = _reduce_args(dd, di, q, other, region)
+    return _C.field_reduce_launch_info(native, di, q, curr, qb, other_curr, region, max_blocks)
+
+
+def field_reduce_supported(dd, di: int, q: int, other=None) -> bool:
+    """True when `field_reduce` takes quantity q (and `other`) of local sub-domain di: fp32 / fp64 quantities (or
+    opaque 4- / 8-byte elements) of the same element size."""
+    return _C.field_reduce_supported(getattr(dd, "native", dd), di, q, -1 if other is None else int(other))
+
+
 def star_supported(dd, di: int, q: int, weights) -> bool:
     """True when `star_apply` can run `weights` on quantity q of local sub-domain di: an fp32 / fp64 quantity (or
     opaque 4- / 8-byte elements), radius 1..3 and all six face radii of the domain >= that radius."""

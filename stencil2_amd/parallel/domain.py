@@ -72,6 +72,29 @@ class DistributedDomain:
     def origin(self, di: int):
         return self._dd.get_origin(di)
 
+    # -------- field reductions --------
+    def reduce(self, q: int, other=None, curr: bool = True, other_curr: bool = False, local: bool = False):
+        """FieldStats of quantity q over the whole grid's compute region: count, nonfinite, sum, sum_abs, sum_sq, min,
+        max (and l1, l2, linf); with `other` of e = q - other, plus dot = sum of q * other. `curr` / `other_curr` pick
+        each operand's curr or next buffer. Collective unless `local`; every rank returns identical bits, and the
+        same call returns the same bits every time (no atomics, fixed combine order)."""
+        return self._dd.reduce(int(q), None if other is None else int(other), bool(curr), bool(other_curr), bool(local))
+
+    def norm(self, q: int, p=2, curr: bool = True) -> float:
+        """the 1-, 2- or "inf"-norm of quantity q (linf is nan when a cell is not finite)"""
+        if p not in (1, 2, "inf"):
+            raise ValueError(f"norm p must be 1, 2 or 'inf', not {p!r}")
+        s = self.reduce(q, curr=curr)
+        return s.l1 if p == 1 else s.l2 if p == 2 else s.linf
+
+    def dot(self, qa: int, qb: int) -> float:
+        """sum over the grid of curr(qa) * curr(qb), accumulated in double"""
+        return self.reduce(qa, other=qb, other_curr=True).dot
+
+    def residual(self, q: int):
+        """FieldStats of curr(q) - next(q): after a single step and swap, the change that step made"""
+        return self.reduce(q, other=q, other_curr=False)
+
     def fill_from_global(self, q: int, fn, include_halo: bool = False):
         """Set every local cell of quantity q to fn(gz, gy, gx) (torch index tensors of global coordinates)."""
         for di, d in enumerate(self.domains()):

@@ -7,9 +7,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "stencil/domain/distributed_domain.hpp"
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/domain/packer.hpp"
 #include "stencil/kernels/field_reduce.hpp"
@@ -62,7 +64,7 @@ int main(int argc, char **argv) {
   p.option(&n, "--n", "cube edge").option(&iters, "--iters", "timed launches per config")
       .option(&reps, "--reps", "repetitions of the whole sweep (interleaved)")
       .option(&only, "--only", "run only 'lds', 'reg', 'copy', 'star' (weighted stars of radius 1-3 beside stencil7) or 'reduce' (field "
-                             "reductions beside the single-step sweep)");
+                             "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -377,6 +379,104 @@ int main(int argc, char **argv) {
         const double us = timeit([&] { stencil_star_apply(l3, 0, reg3, w, s, t); });
         std::printf("stencil_star,%d,2,%d,%.2f,%.1f,%.3f,path%d\n", r, li.zchunk, us, cells / us / 1e3,
                     cells * 8 / us / 1e6, li.path);
+      }
+    }
+  }
+  if (only == "bc") {
+    // Boundary fill beside the periodic exchange of the same domain (fp32, face radius 3, one GPU): (a) the exchange
+    // with every axis a same-GPU self copy (Kernel method), (b) apply_boundary with all six faces Mirror, (c) with
+    // AntiMirror; both move the face cells (a) moves. Interleaved per round in one process, each call timed on its own,
+    // blocking; medians over reps x iters calls, and `stream_us`, the mean of iters back-to-back launches between two
+    // events. Then (b) with non-temporal row stores, and a star step (exchange, fill, star_apply, swap) periodic
+    // against all-Mirror at radius 1 and 3.
+    auto make_dd = [&](int r, const FaceCondition *fc) {
+      auto dd = std::make_unique<DistributedDomain>(n, n, n);
+      dd->set_radius(Radius::face_edge_corner(r, 0, 0));
+      dd->set_methods(MethodFlags::Kernel);
+      dd->set_gpus({0});
+      dd->add_data<float>("u");
+      if (fc) {
+        BoundaryConditions bc;
+        for (int a = 0; a < 3; ++a) bc.set_axis(a, *fc, *fc);
+        dd->set_boundary_conditions(bc);
+      }
+      dd->realize();
+      jacobi_init(dd->domains()[0], 0, dd->domains()[0].get_full_region(), s);
+      s.sync();
+      return dd;
+    };
+    const FaceCondition mir = FaceCondition::mirror(), anti = FaceCondition::antimirror(0.5);
+    auto ddP = make_dd(3, nullptr), ddM = make_dd(3, &mir), ddA = make_dd(3, &anti);
+    auto blocking_us = [&](auto &&fn, std::vector<double> &out) {
+      const auto t0 = std::chrono::steady_clock::now();
+      fn();
+      HIP_CHECK(hipStreamSynchronize(s));
+      out.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    };
+    auto median = [](std::vector<double> v) {
+      std::sort(v.begin(), v.end());
+      return v.empty() ? 0.0 : (v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]));
+    };
+    auto xchg = [&] { ddP->exchange_async(s); };
+    auto fillM = [&] { ddM->apply_boundary(s); };
+    auto fillA = [&] { ddA->apply_boundary(s); };
+    for (int i = 0; i < 3; ++i) { // warm-up: first launches, table upload
+      xchg();
+      fillM();
+      fillA();
+    }
+    s.sync();
+    std::vector<double> ux, um, ua, unt;
+    for (int rep = 0; rep < std::max(reps, 1); ++rep)
+      for (int i = 0; i < iters; ++i) {
+        blocking_us(xchg, ux);
+        blocking_us(fillM, um);
+        blocking_us(fillA, ua);
+        set_boundary_fill_nontemporal(true);
+        blocking_us(fillM, unt);
+        set_boundary_fill_nontemporal(false);
+      }
+    const double mx = median(ux), mm = median(um), ma = median(ua), mnt = median(unt);
+    const double sx = timeit(xchg), sm = timeit(fillM), sa = timeit(fillA);
+    set_boundary_fill_nontemporal(true);
+    const double snt = timeit(fillM);
+    set_boundary_fill_nontemporal(false);
+    std::vector<FillRequest> rq(1);
+    rq[0].bc = ddM->boundary_conditions(0);
+    const FillLaunchInfo li = boundary_fill_launch_info(ddM->domains()[0], ddM->size(), rq);
+    const double ghostBytes = 4.0 * (double(n + 6) * (n + 6) * (n + 6) - double(n) * n * n);
+    std::printf("kernel,n,path,blocks,median_us,stream_us,ghost_MB\n");
+    std::printf("exchange_periodic,%lld,-,-,%.2f,%.2f,%.2f\n", (long long)n, mx, sx,
+                double(ddP->exchange_bytes_for_method(MethodFlags::All)) / 1e6);
+    std::printf("fill_mirror,%lld,%d,%lld,%.2f,%.2f,%.2f\n", (long long)n, li.path, (long long)li.blocks, mm, sm, ghostBytes / 1e6);
+    std::printf("fill_antimirror,%lld,%d,%lld,%.2f,%.2f,%.2f\n", (long long)n, li.path, (long long)li.blocks, ma, sa, ghostBytes / 1e6);
+    std::printf("fill_mirror_nontemporal,%lld,%d,%lld,%.2f,%.2f,%.2f\n", (long long)n, li.path, (long long)li.blocks, mnt, snt,
+                ghostBytes / 1e6);
+    const bool met = mm <= 1.5 * mx && ma <= 1.5 * mx && sm <= 1.5 * sx && sa <= 1.5 * sx;
+    std::printf("bc_condition,fill_le_1.5x_exchange,median %.2f %.2f vs %.2f,stream %.2f %.2f vs %.2f,%s\n", mm, ma, 1.5 * mx, sm,
+                sa, 1.5 * sx, met ? "met" : "MISSED");
+    ddA.reset();
+    // a star step, periodic against all-Mirror
+    std::printf("kernel,radius,boundary,step_us\n");
+    for (int r : {1, 3}) {
+      StarWeights w;
+      w.radius = r;
+      w.center = 0.25;
+      for (int ax = 0; ax < 3; ++ax)
+        for (int sd = 0; sd < 2; ++sd)
+          for (int k = 0; k < r; ++k) w.w[ax][sd][k] = 0.125 / r;
+      auto dp = r == 3 ? std::move(ddP) : make_dd(r, nullptr);
+      auto dm = r == 3 ? std::move(ddM) : make_dd(r, &mir);
+      StencilTune t;
+      for (int which = 0; which < 2; ++which) {
+        DistributedDomain &dd = which ? *dm : *dp;
+        const double us = timeit([&] {
+          dd.exchange_async(s);
+          if (which) dd.apply_boundary(s);
+          stencil_star_apply(dd.domains()[0], 0, dd.domains()[0].get_compute_region(), w, s, t);
+          dd.swap();
+        });
+        std::printf("star_step,%d,%s,%.2f\n", r, which ? "mirror" : "periodic", us);
       }
     }
   }

@@ -27,6 +27,7 @@
 #include "stencil/core/boundary.hpp"
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/domain/packer.hpp"
+#include "stencil/kernels/boundary_fill.hpp"
 #include "stencil/kernels/field_reduce.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/rt/stream.hpp"
@@ -192,6 +193,15 @@ public:
   // global boundary condition (default periodic everywhere). No message crosses a non-periodic face.
   void set_boundary(const Boundary &b) { boundary_ = b; }
   const Boundary &boundary() const { return boundary_; }
+  // physical boundary conditions (stencil/core/boundary.hpp): how apply_boundary() fills the ghost cells beyond the
+  // non-periodic faces of the global grid. The grid's default for every quantity; also sets set_boundary(bc.boundary()).
+  // Without it a non-periodic face is Open: its ghost cells stay as the application left them.
+  void set_boundary_conditions(const BoundaryConditions &bc);
+  // the kinds and values of one quantity (e.g. a velocity component that is AntiMirror normal to a wall and Mirror
+  // along it); its periodic flags must equal the grid's
+  void set_boundary_conditions(int64_t q, const BoundaryConditions &bc);
+  // the conditions in force for quantity q: its override, else the grid's default, else Open where non-periodic
+  BoundaryConditions boundary_conditions(int64_t q) const;
   template <typename T> DataHandle<T> add_data(const std::string &name = "") {
     return DataHandle<T>(add_data(int64_t(sizeof(T)), name, dtype_of<T>()), name);
   }
@@ -336,6 +346,16 @@ public:
   bool gated_send_supported(int skipAxes, bool withTranslate = false) const;
   void swap();
 
+  // ---- physical boundaries (stencil/kernels/boundary_fill.hpp) ----
+  // Fill the ghost cells beyond the non-periodic faces of every quantity (curr buffers), or of one quantity (curr or
+  // next), on every local sub-domain: one launch per sub-domain that touches such a face, enqueued on `stream` of its
+  // device (null: the null stream). Not collective, returns at once. It belongs after the exchange has landed: after
+  // a blocking exchange(), or after wait_exchange(di, stream) on the same stream. exchange() never calls it.
+  void apply_boundary(hipStream_t stream = nullptr);
+  void apply_boundary(int64_t q, bool curr = true, hipStream_t stream = nullptr);
+  // the device tables of local domain di (built on the first fill with a given item list)
+  BoundaryFillCache &fill_cache(size_t di);
+
   // ---- field reductions (stencil/kernels/field_reduce.hpp) ----
   // FieldStats of quantity qa (curr or next), or of the difference and dot product of (qa, currA) and (qb, currB),
   // over the compute region of the whole grid. Collective unless `local`. One reduction per local sub-domain is
@@ -377,6 +397,10 @@ private:
   std::shared_ptr<comm::ProcGroup> pg_;
   Radius radius_;
   Boundary boundary_;
+  bool bcSet_ = false;
+  BoundaryConditions bc_;                        // the grid's default (bcSet_)
+  std::map<int64_t, BoundaryConditions> bcQuantity_; // per-quantity overrides
+  void check_boundary_conditions() const;        // realize(): dtype and thickness refusals
   std::vector<int> gpus_;
   std::vector<int64_t> elemSize_;
   std::vector<std::string> names_;
@@ -420,6 +444,7 @@ private:
   std::unique_ptr<Placement> placement_;
   std::vector<LocalDomain> domains_;
   std::vector<std::unique_ptr<ReduceScratch>> reduceScratch_; // per local domain, allocated on first use
+  std::vector<std::unique_ptr<BoundaryFillCache>> fillCache_; // per local domain, allocated on first use
   std::vector<ExchangePlanEntry> plan_;
   std::vector<std::array<uint8_t, 27>> remoteHalo_; // per local domain, per halo side: filled by a non-Kernel method
   std::array<uint64_t, 5> bytesPerMethod_{}; // indexed by log2(method)

@@ -205,6 +205,39 @@ PYBIND11_MODULE(_C, m) {
       .def("wraps", [](const Boundary &b, int x, int y, int z) { return b.wraps(Dim3(x, y, z)); })
       .def("all_periodic", &Boundary::all_periodic)
       .def("__eq__", [](const Boundary &a, const Boundary &b) { return a == b; });
+  py::enum_<FaceKind>(m, "FaceKind")
+      .value("Periodic", FaceKind::Periodic)
+      .value("Open", FaceKind::Open)
+      .value("Constant", FaceKind::Constant)
+      .value("Mirror", FaceKind::Mirror)
+      .value("AntiMirror", FaceKind::AntiMirror);
+  py::class_<FaceCondition>(m, "FaceCondition")
+      .def(py::init<>())
+      .def_readwrite("kind", &FaceCondition::kind)
+      .def_readwrite("value", &FaceCondition::value)
+      .def_static("periodic", &FaceCondition::periodic)
+      .def_static("open", &FaceCondition::open)
+      .def_static("constant", &FaceCondition::constant, py::arg("value"))
+      .def_static("mirror", &FaceCondition::mirror)
+      .def_static("antimirror", &FaceCondition::antimirror, py::arg("value"))
+      .def("__eq__", [](const FaceCondition &a, const FaceCondition &b) { return a == b; })
+      .def("__repr__", [](const FaceCondition &c) {
+        static const char *names[] = {"periodic", "open", "constant", "mirror", "antimirror"};
+        std::ostringstream o;
+        o << "FaceCondition." << names[int(c.kind)] << "(";
+        if (c.kind == FaceKind::Constant || c.kind == FaceKind::AntiMirror) o << c.value;
+        o << ")";
+        return o.str();
+      });
+  py::class_<BoundaryConditions>(m, "BoundaryConditions")
+      .def(py::init<>())
+      .def("set_face", &BoundaryConditions::set_face, py::arg("x"), py::arg("y"), py::arg("z"), py::arg("cond"))
+      .def("set_axis", &BoundaryConditions::set_axis, py::arg("axis"), py::arg("lo"), py::arg("hi"))
+      .def("face", &BoundaryConditions::face, py::arg("x"), py::arg("y"), py::arg("z"))
+      .def("boundary", &BoundaryConditions::boundary)
+      .def("all_periodic", &BoundaryConditions::all_periodic)
+      .def("__eq__", [](const BoundaryConditions &a, const BoundaryConditions &b) { return a == b; })
+      .def("__copy__", [](const BoundaryConditions &b) { return BoundaryConditions(b); });
 
   py::enum_<MethodFlags>(m, "MethodFlags", py::arithmetic())
       .value("None_", MethodFlags::None)
@@ -682,6 +715,25 @@ PYBIND11_MODULE(_C, m) {
       .def("set_radius", py::overload_cast<int64_t>(&DistributedDomain::set_radius))
       .def("set_radius", py::overload_cast<const Radius &>(&DistributedDomain::set_radius))
       .def("set_boundary", &DistributedDomain::set_boundary)
+      .def("set_boundary_conditions",
+           py::overload_cast<const BoundaryConditions &>(&DistributedDomain::set_boundary_conditions), py::arg("bc"),
+           "the grid's boundary conditions for every quantity (before realize); also sets set_boundary(bc.boundary())")
+      .def("set_boundary_conditions",
+           py::overload_cast<int64_t, const BoundaryConditions &>(&DistributedDomain::set_boundary_conditions),
+           py::arg("q"), py::arg("bc"), "the kinds and values of one quantity; periodic flags as the grid's")
+      .def("boundary_conditions", &DistributedDomain::boundary_conditions, py::arg("q"))
+      .def("apply_boundary",
+           [](DistributedDomain &d, py::object q, bool curr, uintptr_t stream) {
+             if (q.is_none()) {
+               STENCIL_REQUIRE(curr, "apply_boundary() of every quantity fills the curr buffers");
+               d.apply_boundary(reinterpret_cast<hipStream_t>(stream));
+             } else {
+               d.apply_boundary(q.cast<int64_t>(), curr, reinterpret_cast<hipStream_t>(stream));
+             }
+           },
+           py::arg("q") = py::none(), py::arg("curr") = true, py::arg("stream") = 0,
+           "fill the ghost cells beyond the non-periodic faces (every quantity, or quantity q) on every local "
+           "sub-domain; asynchronous on `stream`, after the exchange has landed")
       .def("boundary", &DistributedDomain::boundary)
       .def("radius", &DistributedDomain::radius)
       .def("add_data",
@@ -905,6 +957,44 @@ PYBIND11_MODULE(_C, m) {
           return o;
         },
         py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("tune"));
+  // ---------------- boundary fill ----------------
+  auto fill_requests = [](const std::vector<int64_t> &qs, const std::vector<BoundaryConditions> &bcs, bool curr) {
+    STENCIL_REQUIRE(qs.size() == bcs.size(), "boundary fill: " << qs.size() << " quantities, " << bcs.size() << " conditions");
+    std::vector<FillRequest> reqs(qs.size());
+    for (size_t i = 0; i < qs.size(); ++i) {
+      reqs[i].q = qs[i];
+      reqs[i].curr = curr;
+      reqs[i].bc = bcs[i];
+    }
+    return reqs;
+  };
+  m.def("boundary_fill_supported",
+        [](DistributedDomain &dd, size_t di, int64_t q, const BoundaryConditions &bc) {
+          return boundary_fill_supported(dd.domains().at(di), dd.size(), q, bc);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("q"), py::arg("bc"));
+  m.def("boundary_fill",
+        [fill_requests](DistributedDomain &dd, size_t di, const std::vector<int64_t> &qs,
+                        const std::vector<BoundaryConditions> &bcs, bool curr, uintptr_t stream) {
+          boundary_fill_enqueue(dd.domains().at(di), dd.size(), fill_requests(qs, bcs, curr), dd.fill_cache(di),
+                                reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qs"), py::arg("bcs"), py::arg("curr") = true, py::arg("stream") = 0);
+  m.def("boundary_fill_launch_info",
+        [fill_requests](DistributedDomain &dd, size_t di, const std::vector<int64_t> &qs,
+                        const std::vector<BoundaryConditions> &bcs) {
+          // what boundary_fill would run (nothing is launched)
+          const FillLaunchInfo r = boundary_fill_launch_info(dd.domains().at(di), dd.size(), fill_requests(qs, bcs, true));
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["boxes"] = r.boxes;
+          o["blocks"] = r.blocks;
+          o["launches"] = r.launches;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qs"), py::arg("bcs"));
+  m.def("set_boundary_fill_nontemporal", &set_boundary_fill_nontemporal, py::arg("on"));
   py::class_<X3PlanInfo>(m, "X3PlanInfo")
       .def_readonly("parts", &X3PlanInfo::parts)
       .def_readonly("blocks", &X3PlanInfo::blocks)

@@ -376,6 +376,7 @@ void DistributedDomain::realize() {
     }
   }
   timePlacement_ = setup_time(now_s() - t0);
+  check_boundary_conditions();
 
   // ---- local domains ----
   t0 = now_s();

@@ -28,8 +28,11 @@ from . import _C  # noqa: E402
 from ._C import (  # noqa: E402,F401
     Backend,
     Boundary,
+    BoundaryConditions,
     Dim3,
     DType,
+    FaceCondition,
+    FaceKind,
     MethodFlags,
     NodeAwarePlacement,
     NodePartition,
@@ -68,7 +71,7 @@ from .models.stencil_model import Jacobi3D, AstarothSim, StencilModel  # noqa: E
 from .models.star_model import StarStencil3D  # noqa: E402,F401
 
 __all__ = [
-    "Backend", "Boundary", "Dim3", "DType", "MethodFlags", "PlacementStrategy", "Radius", "Rect3", "Statistics", "StencilKind",
+    "Backend", "Boundary", "BoundaryConditions", "FaceCondition", "FaceKind", "Dim3", "DType", "MethodFlags", "PlacementStrategy", "Radius", "Rect3", "Statistics", "StencilKind",
     "DistributedDomain", "Jacobi3D", "AstarothSim", "StencilModel", "StarStencil3D", "init_process_group", "get_group",
     "TransportOptions", "build_info", "RankPartition", "NodePartition", "TrivialPlacement", "NodeAwarePlacement", "qap_solve", "qap_solve_catch",
 ]

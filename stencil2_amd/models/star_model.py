@@ -1,8 +1,10 @@
-"""A weighted star stencil (radius 1-3, caller-supplied weights) stepped over a periodic distributed grid.
+"""A weighted star stencil (radius 1-3, caller-supplied weights) stepped over a distributed grid, periodic or with
+physical boundary conditions.
 
 ``StarStencil3D`` is a thin Python class over ``parallel.DistributedDomain``: each ``step()`` exchanges the face halos
-to depth ``weights.radius``, applies ``ops.star_apply`` to every quantity of every local sub-domain and swaps the
-buffers. Results are bitwise equal to ``ops.star_step_reference`` on the gathered global grid.
+to depth ``weights.radius``, fills the ghost cells beyond the non-periodic faces (``boundary``: a
+``BoundaryConditions``; None = periodic), applies ``ops.star_apply`` to every quantity of every local sub-domain and
+swaps the buffers. Results are bitwise equal to ``ops.star_step_reference`` on the gathered global grid.
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ from ..parallel.domain import DistributedDomain
 
 class StarStencil3D:
     def __init__(self, size, weights, quantities: int = 1, fp64: bool = False, gpus=None, backend=None,
-                 methods=_C.MethodFlags.All, group=None, axis_cost=None, tune=None):
+                 methods=_C.MethodFlags.All, group=None, axis_cost=None, tune=None, boundary=None):
         if weights.radius not in (1, 2, 3):
             raise ValueError(f"star radius must be 1, 2 or 3, not {weights.radius}")
         self.weights = weights
@@ -31,6 +33,9 @@ class StarStencil3D:
         if axis_cost is not None:  # NodeAware cut costs per axis (the cheapest axis is cut first)
             dd.set_axis_cost(_C.Dim3(*axis_cost))
         self._qs = [dd.add_data(f"u{q}", self.dtype) for q in range(quantities)]
+        self.boundary = boundary
+        if boundary is not None:
+            dd.set_boundary_conditions(boundary)
         dd.realize()
         for di in range(dd.num_domains()):
             for q in self._qs:
@@ -50,6 +55,8 @@ class StarStencil3D:
     def step(self):
         dd = self._dd
         dd.exchange()  # blocking; orders itself after the null stream, where the kernels below run
+        if self.boundary is not None:
+            dd.apply_boundary()  # one launch per sub-domain that touches a non-periodic face
         for di in range(dd.num_domains()):
             for q in self._qs:
                 star_apply(dd, di, q, self.weights, tune=self.tune)

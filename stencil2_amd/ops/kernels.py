@@ -150,6 +150,48 @@ def field_reduce_supported(dd, di: int, q: int, other=None) -> bool:
     return _C.field_reduce_supported(getattr(dd, "native", dd), di, q, -1 if other is None else int(other))
 
 
+def _fill_args(dd, q, bc):
+    """(native, quantities, conditions): q None = every quantity whose conditions fill a face, as apply_boundary()"""
+    native = getattr(dd, "native", dd)
+    if q is None:
+        qs = list(range(native.domain(0).num_data()))
+    else:
+        qs = [int(v) for v in q] if isinstance(q, (list, tuple)) else [int(q)]
+    if bc is None:
+        bcs = [native.boundary_conditions(v) for v in qs]
+    else:
+        bcs = list(bc) if isinstance(bc, (list, tuple)) else [bc] * len(qs)
+    return native, qs, bcs
+
+
+def boundary_apply(dd, di: int, q, bc=None, curr: bool = True, stream: int = 0):
+    """Fill the ghost cells of quantity q (an index, a list, or None = every quantity) of local sub-domain di beyond
+    the non-periodic faces of the global grid under `bc` (_C.BoundaryConditions, default the domain's conditions for
+    q): Constant faces T(v), Mirror faces the mirror cell, AntiMirror faces T(2 v) - mirror cell, Open faces left
+    alone; edges and corners resolve z, then y, then x (ops.boundary_fill_reference). One launch for the whole list,
+    asynchronous on `stream`; only ghost cells are written and only other cells are read. It belongs after the
+    exchange has landed (csrc/src/kernels/boundary_fill.hip)."""
+    native, qs, bcs = _fill_args(dd, q, bc)
+    _C.boundary_fill(native, di, qs, bcs, curr, stream)
+
+
+def boundary_launch_info(dd, di: int, q=None, bc=None) -> dict:
+    """What `boundary_apply` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the row / column kernel of the aligned vector layout, "generic": one thread per ghost cell, "host",
+    "none": the sub-domain touches no face that is filled), `boxes` (disjoint boxes of ghost cells over all
+    quantities), `blocks` and `launches` (one per 16 quantities)."""
+    native, qs, bcs = _fill_args(dd, q, bc)
+    return _C.boundary_fill_launch_info(native, di, qs, bcs)
+
+
+def boundary_supported(dd, di: int, q: int, bc=None) -> bool:
+    """True when `boundary_apply` takes quantity q of local sub-domain di under `bc`: an fp32 / fp64 quantity (or
+    opaque 4- / 8-byte elements) whose extent along every Mirror / AntiMirror face the sub-domain touches is at least
+    that side's face radius."""
+    native, qs, bcs = _fill_args(dd, q, bc)
+    return _C.boundary_fill_supported(native, di, qs[0], bcs[0])
+
+
 def star_supported(dd, di: int, q: int, weights) -> bool:
     """True when `star_apply` can run `weights` on quantity q of local sub-domain di: an fp32 / fp64 quantity (or
     opaque 4- / 8-byte elements), radius 1..3 and all six face radii of the domain >= that radius."""

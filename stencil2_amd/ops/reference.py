@@ -102,23 +102,150 @@ def astaroth_init_reference(size_xyz, radius: int, period: float, dtype=torch.fl
     return torch.sin(k * x + k * y + k * z).to(dtype)
 
 
-def star_step_reference(u: torch.Tensor, weights) -> torch.Tensor:
-    """One weighted star step (`weights`: _C.StarWeights, see ops.star) on a periodic global (z, y, x) grid: the
-    oracle of `star_apply`. acc = center * u, then per axis x, y, z and k = 1..radius: acc + w[-k] * u(c - k), then
+def star_step_reference(u: torch.Tensor, weights, boundary=None) -> torch.Tensor:
+    """One weighted star step (`weights`: _C.StarWeights, see ops.star) on a global (z, y, x) grid: the oracle of
+    `star_apply`. acc = center * u, then per axis x, y, z and k = 1..radius: acc + w[-k] * u(c - k), then
     acc + w[+k] * u(c + k). The weights are 0-dim tensors of u's dtype (one conversion from double) and every product
-    and every sum is a separate op, so each is rounded on its own in that dtype."""
+    and every sum is a separate op, so each is rounded on its own in that dtype. `boundary` (_C.BoundaryConditions):
+    the neighbours beyond a non-periodic face come from `pad_reference`; None is the periodic grid."""
     def wt(v):
         return torch.tensor(v, dtype=torch.float64).to(u.dtype).to(u.device)
 
+    R = weights.radius
+    if boundary is None:
+        def nb(k, dim):  # u(c - k e)
+            return torch.roll(u, k, dim)
+    else:
+        p = pad_reference(u, R, boundary)
+        Z, Y, X = u.shape
+
+        def nb(k, dim):
+            lo = [R, R, R]
+            lo[dim] -= k
+            return p[lo[0]:lo[0] + Z, lo[1]:lo[1] + Y, lo[2]:lo[2] + X]
+
     acc = wt(weights.center) * u
     for ax, dim in enumerate((2, 1, 0)):
-        for k in range(1, weights.radius + 1):
-            term = wt(weights.get(ax, 0, k)) * torch.roll(u, k, dim)  # u(c - k e)
+        for k in range(1, R + 1):
+            term = wt(weights.get(ax, 0, k)) * nb(k, dim)  # u(c - k e)
             acc = acc + term
-            term = wt(weights.get(ax, 1, k)) * torch.roll(u, -k, dim)  # u(c + k e)
+            term = wt(weights.get(ax, 1, k)) * nb(-k, dim)  # u(c + k e)
             acc = acc + term
     return acc
 
 
+# ---- physical boundary conditions (csrc/include/stencil/core/boundary.hpp) ----
+_FACES = ((0, (-1, 0, 0), (1, 0, 0)), (1, (0, -1, 0), (0, 1, 0)), (2, (0, 0, -1), (0, 0, 1)))  # axis, low dir, high dir
+
+
+def _kind_name(cond):
+    return str(cond.kind).split(".")[-1]
+
+
+def _anti_c(value, dtype, device):
+    """T(2.0 * v): the double product, converted to the field's type once"""
+    return torch.tensor(2.0 * value, dtype=torch.float64).to(dtype).to(device)
+
+
+def pad_reference(u_global: torch.Tensor, radius: int, bc) -> torch.Tensor:
+    """The global (z, y, x) grid padded by `radius` cells on every side, sequentially along x, then y, then z, each
+    pass over the whole padded extent of the axes before it: periodic axes wrapped, Constant faces T(v), Mirror faces
+    the mirror cell, AntiMirror faces T(2.0 * v) - mirror cell (one subtraction in the field's type). Cells beyond an
+    Open face are NaN (nothing defines them)."""
+    r = int(radius)
+    p = u_global
+    for ax, lo_dir, hi_dir in _FACES:
+        dim = 2 - ax
+        n = p.shape[dim]
+        conds = (bc.face(*lo_dir), bc.face(*hi_dir))
+        parts = []
+        for side, cond in enumerate(conds):
+            k = _kind_name(cond)
+            if k == "Periodic":
+                idx = torch.arange(n - r, n) if side == 0 else torch.arange(0, r)
+                g = p.index_select(dim, (idx % n).to(p.device))
+            elif k == "Open":
+                shape = list(p.shape)
+                shape[dim] = r
+                g = torch.full(shape, float("nan"), dtype=p.dtype, device=p.device)
+            elif k == "Constant":
+                shape = list(p.shape)
+                shape[dim] = r
+                g = torch.full(shape, 0, dtype=p.dtype, device=p.device) + \
+                    torch.tensor(cond.value, dtype=torch.float64).to(p.dtype).to(p.device)
+            else:
+                # ghost at distance k outside <- interior at distance k inside: low face r-1..0, high face n-1..n-r
+                idx = torch.arange(r - 1, -1, -1) if side == 0 else torch.arange(n - 1, n - 1 - r, -1)
+                if r > n:
+                    raise ValueError(f"mirror of {r} cells on an axis of {n}")
+                g = p.index_select(dim, idx.to(p.device))
+                if k == "AntiMirror":
+                    g = _anti_c(cond.value, p.dtype, p.device) - g
+            parts.append(g)
+        p = torch.cat([parts[0], p, parts[1]], dim=dim)
+    return p
+
+
+def boundary_fill_reference(raw: torch.Tensor, origin, size, radius_lo, radius_hi, grid, bc, return_mask: bool = False):
+    """The composed map of csrc/include/stencil/kernels/boundary_fill.hpp applied to one sub-domain's raw (z, y, x)
+    tensor (halo included; a copy is returned): `origin` / `size` (x, y, z) of the sub-domain, `radius_lo` /
+    `radius_hi` its face radii per axis (x, y, z), `grid` the global size. For every cell resolve z, then y, then x:
+    beyond a Constant face the chain ends with T(v); beyond Mirror / AntiMirror the coordinate is reflected; inside,
+    in an exchanged halo, or beyond an Open face after an earlier axis resolved it stays; then the source cell is
+    loaded and the AntiMirror subtractions applied x, then y, then z. Cells whose first face is Open, and cells beyond
+    no non-periodic face, keep their content. `return_mask`: also the boolean mask of the cells written."""
+    rawz, rawy, rawx = raw.shape
+    ext = (rawx, rawy, rawz)
+    dev = raw.device
+    coords = [None, None, None]
+    coords[0] = torch.arange(rawx, device=dev).view(1, 1, -1).expand(rawz, rawy, rawx).clone()
+    coords[1] = torch.arange(rawy, device=dev).view(1, -1, 1).expand(rawz, rawy, rawx).clone()
+    coords[2] = torch.arange(rawz, device=dev).view(-1, 1, 1).expand(rawz, rawy, rawx).clone()
+    seen = torch.zeros(raw.shape, dtype=torch.bool, device=dev)
+    skip = torch.zeros_like(seen)
+    is_const = torch.zeros_like(seen)
+    const_v = torch.zeros_like(raw)
+    anti = [None, None, None]  # per axis: (mask, c tensor)
+    for ax in (2, 1, 0):
+        _, lo_dir, hi_dir = _FACES[ax]
+        lo, hi = 0, ext[ax]
+        conds = [None, None]
+        if _kind_name(bc.face(*lo_dir)) != "Periodic" and origin[ax] == 0 and radius_lo[ax] > 0:
+            lo, conds[0] = radius_lo[ax], bc.face(*lo_dir)
+        if _kind_name(bc.face(*hi_dir)) != "Periodic" and origin[ax] + size[ax] == grid[ax] and radius_hi[ax] > 0:
+            hi, conds[1] = radius_lo[ax] + size[ax], bc.face(*hi_dir)
+        amask = torch.zeros_like(seen)
+        aval = torch.zeros_like(raw)
+        c = coords[ax]
+        for side, cond in enumerate(conds):
+            if cond is None:
+                continue
+            beyond = ((c < lo) if side == 0 else (c >= hi)) & ~is_const & ~skip
+            k = _kind_name(cond)
+            if k == "Open":
+                skip |= beyond & ~seen
+                continue
+            seen |= beyond
+            if k == "Constant":
+                const_v = torch.where(beyond, torch.tensor(cond.value, dtype=torch.float64).to(raw.dtype).to(dev), const_v)
+                is_const |= beyond
+                continue
+            refl = (2 * lo - 1 - c) if side == 0 else (2 * hi - 1 - c)
+            if k == "AntiMirror":
+                amask |= beyond
+                aval = torch.where(beyond, _anti_c(cond.value, raw.dtype, dev), aval)
+            c = torch.where(beyond, refl, c)
+        coords[ax] = c
+        anti[ax] = (amask, aval)
+    v = raw[coords[2], coords[1], coords[0]]
+    v = torch.where(is_const, const_v, v)
+    for ax in (0, 1, 2):
+        amask, aval = anti[ax]
+        v = torch.where(amask, aval - v, v)
+    written = seen & ~skip
+    out = torch.where(written, v, raw)
+    return (out, written) if return_mask else out
+
+
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "pad_reference", "boundary_fill_reference", "math"]

@@ -24,7 +24,10 @@ _TORCH_TO_DT = {
 
 
 class DistributedDomain:
-    """A periodic global grid split into sub-domains (one per GPU, several per process allowed)."""
+    """A global grid split into sub-domains (one per GPU, several per process allowed). Periodic by default;
+    ``set_boundary_conditions(bc)`` / ``set_boundary_conditions(q, bc)`` (before ``realize()``) choose per face and per
+    quantity how the ghost cells beyond a non-periodic face are filled (``_C.BoundaryConditions``), and
+    ``apply_boundary(q=None, curr=True, stream=0)`` fills them after an exchange has landed."""
 
     def __init__(self, x: int, y: int, z: int, group=None):
         self._group = group if group is not None else get_group()

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -64,7 +65,8 @@ int main(int argc, char **argv) {
   p.option(&n, "--n", "cube edge").option(&iters, "--iters", "timed launches per config")
       .option(&reps, "--reps", "repetitions of the whole sweep (interleaved)")
       .option(&only, "--only", "run only 'lds', 'reg', 'copy', 'star' (weighted stars of radius 1-3 beside stencil7) or 'reduce' (field "
-                             "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange)");
+                             "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange) or "
+                             "'axpby' (field algebra beside the field reductions)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -526,6 +528,75 @@ int main(int argc, char **argv) {
     const FieldStats r = scratch.result();
     std::printf("reduce_check,count,%lld,nonfinite,%lld,sum_sq,%.17g\n", (long long)r.count, (long long)r.nonfinite, r.sum_sq);
     std::printf("reduce_condition,one_operand_median_us,%.2f,sweep_median_us,%.2f,%s\n", m1, m7, m1 <= m7 ? "met" : "MISSED");
+  }
+  if (only == "axpby") {
+    // Field algebra beside the field reductions, on a domain of its own with three quantities r, p, w, all in one
+    // invocation, every call timed as under 'reduce' (blocking medians, interleaved per round, and back-to-back stream
+    // time). The CG residual update r <- r - alpha next(p) with stats reads 8 B and writes 4 B per cell; the
+    // one-operand and the two-operand reduction (unchanged code) together move the same 12 B per cell, so the fused
+    // update must take at most 1.25 x the sum of their medians.
+    LocalDomain ad(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
+    ad.set_radius(1);
+    for (const char *name : {"r", "p", "w"}) ad.add_data<float>(name);
+    ad.realize();
+    const Rect3 areg = ad.get_compute_region();
+    for (int q = 0; q < 3; ++q) {
+      jacobi_init(ad, q, ad.get_full_region(), s);
+      field_axpby_enqueue(ad, FieldRef(q, false), 1.0, FieldRef(q, true), 0.0, FieldRef(), areg, s);
+    }
+    s.sync();
+    ReduceScratch scratch;
+    auto blocking_us = [&](auto &&fn, std::vector<double> &out) {
+      const auto t0 = std::chrono::steady_clock::now();
+      fn();
+      HIP_CHECK(hipStreamSynchronize(s));
+      out.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    };
+    auto median = [](std::vector<double> v) {
+      std::sort(v.begin(), v.end());
+      return v.empty() ? 0.0 : (v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]));
+    };
+    const FieldRef r(0, true), ap(1, false), w(2, true), none;
+    const double alpha = 1e-4;
+    std::vector<std::function<void()>> fns = {
+        [&] { field_reduce_enqueue(ad, 0, true, -1, false, areg, scratch, s); },
+        [&] { field_reduce_enqueue(ad, 0, true, 1, false, areg, scratch, s); },
+        [&] { field_axpby_enqueue(ad, w, 0.5, r, 0.0, none, areg, s); },                          // w <- 0.5 r
+        [&] { field_axpby_enqueue(ad, w, 1.0, r, 0.5, w, areg, s); },                             // w <- r + 0.5 w
+        [&] { field_axpby_enqueue(ad, r, 1.0, r, -alpha, ap, areg, s, &scratch); },               // r <- r - alpha Ap, ||r||
+        [&] { field_axpby_enqueue(ad, r, 1.0, r, -alpha, ap, areg, s, &scratch, 0, true); },      // the same, nt stores
+    };
+    const char *names[] = {"field_reduce,1", "field_reduce,2", "field_axpby,1", "field_axpby,2", "field_axpby_stats,2",
+                           "field_axpby_stats_nt,2"};
+    const double bytes[] = {4, 8, 8, 12, 12, 12};
+    const ReduceLaunchInfo rli = field_reduce_launch_info(ad, 0, true, 1, false, areg);
+    const AxpbyLaunchInfo ali[] = {field_axpby_launch_info(ad, w, 0.5, r, 0.0, none, areg),
+                                   field_axpby_launch_info(ad, w, 1.0, r, 0.5, w, areg),
+                                   field_axpby_launch_info(ad, r, 1.0, r, -alpha, ap, areg, true),
+                                   field_axpby_launch_info(ad, r, 1.0, r, -alpha, ap, areg, true, 0, true)};
+    for (int i = 0; i < 3; ++i) // warm-up: first launches, scratch allocation
+      for (auto &f : fns) f();
+    s.sync();
+    std::vector<std::vector<double>> us(fns.size());
+    for (int rep = 0; rep < std::max(reps, 1); ++rep)
+      for (int i = 0; i < iters; ++i)
+        for (size_t k = 0; k < fns.size(); ++k) blocking_us(fns[k], us[k]);
+    std::printf("kernel,operands,path,blocks,median_us,gcells,moved_TBps,stream_us\n");
+    std::vector<double> med(fns.size());
+    for (size_t k = 0; k < fns.size(); ++k) {
+      med[k] = median(us[k]);
+      const double st = timeit(fns[k]);
+      const int path = k < 2 ? rli.path : ali[k - 2].path;
+      const long long blocks = (long long)(k < 2 ? rli.blocks : ali[k - 2].blocks);
+      std::printf("%s,%d,%lld,%.2f,%.1f,%.3f,%.2f\n", names[k], path, blocks, med[k], cells / med[k] / 1e3,
+                  cells * bytes[k] / med[k] / 1e6, st);
+    }
+    const FieldStats fs = scratch.result();
+    std::printf("axpby_check,count,%lld,nonfinite,%lld,sum_sq,%.17g\n", (long long)fs.count, (long long)fs.nonfinite, fs.sum_sq);
+    const double bound = 1.25 * (med[0] + med[1]);
+    std::printf("axpby_condition,fused_update_median_us,%.2f,reduce1_plus_reduce2_median_us,%.2f,ratio,%.3f,bound,1.25,%s\n",
+                med[4], med[0] + med[1], med[4] / (med[0] + med[1]), med[4] <= bound ? "met" : "MISSED");
+    std::printf("axpby_stores,plain_median_us,%.2f,nontemporal_median_us,%.2f\n", med[4], med[5]);
   }
   for (int rep = 0; rep < reps; ++rep)
   if (only == "x2pp") {

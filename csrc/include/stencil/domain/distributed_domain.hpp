@@ -28,6 +28,7 @@
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/domain/packer.hpp"
 #include "stencil/kernels/boundary_fill.hpp"
+#include "stencil/kernels/field_axpby.hpp"
 #include "stencil/kernels/field_reduce.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/rt/stream.hpp"
@@ -366,6 +367,18 @@ public:
   FieldStats reduce(int64_t qa, bool currA = true, int64_t qb = -1, bool currB = false, bool local = false);
   // the reduction scratch (partial slab and pinned result) of local domain di
   ReduceScratch &reduce_scratch(size_t di);
+
+  // ---- field algebra (stencil/kernels/field_axpby.hpp) ----
+  // dst = a x (y.q < 0) or dst = a x + b y over the compute region of every local sub-domain; an operand is
+  // (quantity, curr or next) and dst may alias x and / or y. Every refusal is raised for every local sub-domain before
+  // anything is enqueued; then one launch per sub-domain on `stream` of its device (null: the null stream), as
+  // apply_boundary follows the caller's stream. Without `stats` the call is asynchronous and not collective, and the
+  // returned struct is the identity. With `stats` it waits for `stream` on every device and returns the FieldStats of
+  // the stored values: sub-domains merged in index order and, unless `local`, the ranks' structs allgathered and
+  // merged in rank order (collective; every rank returns identical bits). A poisoned domain refuses a stats call.
+  // The halos of dst are stale afterwards.
+  FieldStats axpby(FieldRef dst, double a, FieldRef x, double b, FieldRef y, bool stats, bool local,
+                   hipStream_t stream = nullptr);
 
   // ---- transport log (wait vs copy of the fused co-located kernels) ----
   // keep the last `exchanges` exchanges' device timestamps (s_memrealtime, 100-MHz constant clock) of every fused

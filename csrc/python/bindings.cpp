@@ -695,7 +695,73 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dd"), py::arg("domain"), py::arg("qa"), py::arg("curr_a"), py::arg("qb"), py::arg("curr_b"),
         py::arg("region"), py::arg("max_blocks") = 0);
 
+  // ---------------- field algebra ----------------
+  m.def("field_axpby_supported",
+        [](DistributedDomain &dd, size_t di, int64_t qdst, int64_t qx, int64_t qy) {
+          return field_axpby_supported(dd.domains().at(di), qdst, qx, qy);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qdst"), py::arg("qx"), py::arg("qy") = -1);
+  m.def("field_axpby",
+        [](DistributedDomain &dd, size_t di, int64_t qdst, bool currDst, double a, int64_t qx, bool currX, double b,
+           int64_t qy, bool currY, const Rect3 &region, uintptr_t stream, bool stats, int maxBlocks,
+           bool nontemporal) -> py::object {
+          // asynchronous without stats; with stats blocking, the scratch the domain's own
+          const LocalDomain &d = dd.domains().at(di);
+          hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+          FieldStats out;
+          {
+            py::gil_scoped_release r;
+            field_axpby_enqueue(d, FieldRef(qdst, currDst), a, FieldRef(qx, currX), b, FieldRef(qy, currY), region, s,
+                                stats ? &dd.reduce_scratch(di) : nullptr, maxBlocks, nontemporal);
+            if (stats) {
+              if (d.backend() == Backend::Device) {
+                d.set_device();
+                HIP_CHECK(hipStreamSynchronize(s));
+              }
+              out = dd.reduce_scratch(di).result();
+            }
+          }
+          if (!stats) return py::none();
+          return py::cast(out);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qdst"), py::arg("curr_dst"), py::arg("a"), py::arg("qx"),
+        py::arg("curr_x"), py::arg("b"), py::arg("qy"), py::arg("curr_y"), py::arg("region"), py::arg("stream") = 0,
+        py::arg("stats") = false, py::arg("max_blocks") = 0, py::arg("nontemporal") = false);
+  m.def("field_axpby_launch_info",
+        [](DistributedDomain &dd, size_t di, int64_t qdst, bool currDst, double a, int64_t qx, bool currX, double b,
+           int64_t qy, bool currY, const Rect3 &region, bool stats, int maxBlocks, bool nontemporal) {
+          // what field_axpby would run (nothing is launched)
+          const AxpbyLaunchInfo r = field_axpby_launch_info(dd.domains().at(di), FieldRef(qdst, currDst), a,
+                                                            FieldRef(qx, currX), b, FieldRef(qy, currY), region, stats,
+                                                            maxBlocks, nontemporal);
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["blocks"] = r.blocks;
+          o["items"] = r.items;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qdst"), py::arg("curr_dst"), py::arg("a"), py::arg("qx"),
+        py::arg("curr_x"), py::arg("b"), py::arg("qy"), py::arg("curr_y"), py::arg("region"), py::arg("stats") = false,
+        py::arg("max_blocks") = 0, py::arg("nontemporal") = false);
+
   py::class_<DistributedDomain, std::shared_ptr<DistributedDomain>>(m, "DistributedDomain")
+      .def("axpby",
+           [](DistributedDomain &d, int64_t qdst, bool currDst, double a, int64_t qx, bool currX, double b, int64_t qy,
+              bool currY, bool stats, bool local, uintptr_t stream) -> py::object {
+             FieldStats out;
+             {
+               py::gil_scoped_release r;
+               out = d.axpby(FieldRef(qdst, currDst), a, FieldRef(qx, currX), b, FieldRef(qy, currY), stats, local,
+                             reinterpret_cast<hipStream_t>(stream));
+             }
+             if (!stats) return py::none();
+             return py::cast(out);
+           },
+           py::arg("qdst"), py::arg("curr_dst"), py::arg("a"), py::arg("qx"), py::arg("curr_x"), py::arg("b"),
+           py::arg("qy"), py::arg("curr_y"), py::arg("stats") = false, py::arg("local") = false, py::arg("stream") = 0,
+           "dst = a x (qy < 0) or a x + b y over the compute region of every local sub-domain; with stats the "
+           "FieldStats of the stored values (collective unless local), else None (asynchronous on `stream`)")
       .def("reduce",
            [](DistributedDomain &d, int64_t q, py::object other, bool curr, bool otherCurr, bool local) {
              const int64_t qb = other.is_none() ? -1 : other.cast<int64_t>();

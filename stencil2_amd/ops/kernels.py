@@ -150,6 +150,46 @@ def field_reduce_supported(dd, di: int, q: int, other=None) -> bool:
     return _C.field_reduce_supported(getattr(dd, "native", dd), di, q, -1 if other is None else int(other))
 
 
+def _axpby_args(dd, di, y, region):
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return native, (-1 if y is None else int(y)), region
+
+
+def field_axpby(dd, di: int, dst: int, a: float, x: int, b: float = 0.0, y=None, dst_curr: bool = True,
+                x_curr: bool = True, y_curr: bool = True, region=None, stream: int = 0, stats: bool = False,
+                max_blocks: int = 0, nontemporal: bool = False):
+    """dst(region) = a * x (y None) or a * x + b * y for quantities of local sub-domain di; `*_curr` pick each
+    operand's curr or next buffer and `region` (global coordinates) defaults to the sub-domain's compute region. a and
+    b are converted to the element type once; every product and the sum is its own rounding in that type, so the
+    result is bitwise equal to `axpby_reference`. dst may alias x and / or y. Only cells of the region are written, so
+    the halos of dst are stale afterwards. Asynchronous on `stream` and returns None; with `stats` it waits for the
+    stream and returns the FieldStats of the stored values, accumulated in the same pass as `field_reduce` would
+    (dot = 0). `max_blocks`: 0 = one round of resident blocks, else exactly that many; `nontemporal`: nt-hinted 16-B
+    stores (csrc/src/kernels/field_axpby.hip)."""
+    native, qy, region = _axpby_args(dd, di, y, region)
+    return _C.field_axpby(native, di, int(dst), bool(dst_curr), float(a), int(x), bool(x_curr), float(b), qy,
+                          bool(y_curr), region, stream, bool(stats), max_blocks, bool(nontemporal))
+
+
+def field_axpby_launch_info(dd, di: int, dst: int, a: float, x: int, b: float = 0.0, y=None, dst_curr: bool = True,
+                            x_curr: bool = True, y_curr: bool = True, region=None, stats: bool = False,
+                            max_blocks: int = 0, nontemporal: bool = False) -> dict:
+    """What `field_axpby` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the row kernel of the aligned vector layout, "generic": one thread per cell, "host", "none": empty
+    region), `blocks` of the launch and `items`, the (row, plane) pairs of the region."""
+    native, qy, region = _axpby_args(dd, di, y, region)
+    return _C.field_axpby_launch_info(native, di, int(dst), bool(dst_curr), float(a), int(x), bool(x_curr), float(b),
+                                      qy, bool(y_curr), region, bool(stats), max_blocks, bool(nontemporal))
+
+
+def field_axpby_supported(dd, di: int, dst: int, x: int, y=None) -> bool:
+    """True when `field_axpby` takes these quantities of local sub-domain di: fp32 / fp64 quantities (or opaque 4- /
+    8-byte elements) of one element size and row pitch."""
+    return _C.field_axpby_supported(getattr(dd, "native", dd), di, int(dst), int(x), -1 if y is None else int(y))
+
+
 def _fill_args(dd, q, bc):
     """(native, quantities, conditions): q None = every quantity whose conditions fill a face, as apply_boundary()"""
     native = getattr(dd, "native", dd)

@@ -134,6 +134,20 @@ def star_step_reference(u: torch.Tensor, weights, boundary=None) -> torch.Tensor
     return acc
 
 
+def axpby_reference(a, x: torch.Tensor, b=None, y=None) -> torch.Tensor:
+    """a * x, or a * x + b * y: the oracle of `field_axpby`. a and b are 0-dim tensors of x's dtype (one conversion
+    from double), and each product and the sum is a separate op, so each is rounded on its own in that dtype. A zero
+    coefficient is multiplied like any other (NaN and Inf propagate)."""
+    def ct(v):
+        return torch.tensor(float(v), dtype=torch.float64).to(x.dtype).to(x.device)
+
+    t = ct(a) * x
+    if y is None:
+        return t
+    s = ct(b) * y
+    return t + s
+
+
 # ---- physical boundary conditions (csrc/include/stencil/core/boundary.hpp) ----
 _FACES = ((0, (-1, 0, 0), (1, 0, 0)), (1, (0, -1, 0), (0, 1, 0)), (2, (0, 0, -1), (0, 0, 1)))  # axis, low dir, high dir
 
@@ -248,4 +262,4 @@ def boundary_fill_reference(raw: torch.Tensor, origin, size, radius_lo, radius_h
 
 
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "pad_reference", "boundary_fill_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "axpby_reference", "pad_reference", "boundary_fill_reference", "math"]

@@ -98,6 +98,25 @@ class DistributedDomain:
         """FieldStats of curr(q) - next(q): after a single step and swap, the change that step made"""
         return self.reduce(q, other=q, other_curr=False)
 
+    # -------- field algebra --------
+    def axpby(self, dst: int, a: float, x: int, b: float = 0.0, y=None, dst_curr: bool = True, x_curr: bool = True,
+              y_curr: bool = True, stats: bool = False, local: bool = False, stream: int = 0):
+        """dst = a * x (y None) or a * x + b * y over the compute region of every local sub-domain (`ops.field_axpby`);
+        `*_curr` pick each operand's curr or next buffer, and dst may alias x and / or y. One launch per sub-domain on
+        `stream`; asynchronous, not collective, returns None. With `stats` it waits for the stream and returns the
+        FieldStats of the stored values from the same pass: collective unless `local`, identical bits on every rank.
+        Only the compute region is written, so the halos of dst are stale: exchange before the next stencil."""
+        return self._dd.axpby(int(dst), bool(dst_curr), float(a), int(x), bool(x_curr), float(b),
+                              -1 if y is None else int(y), bool(y_curr), bool(stats), bool(local), stream)
+
+    def copy(self, dst: int, src: int, dst_curr: bool = True, src_curr: bool = True):
+        """dst = src over the compute regions (an exact copy: axpby with a = 1)"""
+        self.axpby(dst, 1.0, src, dst_curr=dst_curr, x_curr=src_curr)
+
+    def scale(self, q: int, a: float, curr: bool = True):
+        """q = a * q over the compute regions, in place"""
+        self.axpby(q, a, q, dst_curr=curr, x_curr=curr)
+
     def fill_from_global(self, q: int, fn, include_halo: bool = False):
         """Set every local cell of quantity q to fn(gz, gy, gx) (torch index tensors of global coordinates)."""
         for di, d in enumerate(self.domains()):

@@ -51,6 +51,7 @@ inline MethodFlags operator|(MethodFlags a, MethodFlags b) { return MethodFlags(
 inline MethodFlags &operator|=(MethodFlags &a, MethodFlags b) { return a = a | b; }
 inline MethodFlags operator&(MethodFlags a, MethodFlags b) { return MethodFlags(int(a) & int(b)); }
 inline bool operator&&(MethodFlags a, MethodFlags b) { return (int(a) & int(b)) != 0; }
+inline MethodFlags without(MethodFlags a, MethodFlags m) { return MethodFlags(int(a) & ~int(m)); }
 inline bool any(MethodFlags a) { return a != MethodFlags::None; }
 std::string to_string(MethodFlags m);
 
@@ -413,7 +414,6 @@ private:
   bool bcSet_ = false;
   BoundaryConditions bc_;                        // the grid's default (bcSet_)
   std::map<int64_t, BoundaryConditions> bcQuantity_; // per-quantity overrides
-  void check_boundary_conditions() const;        // realize(): dtype and thickness refusals
   std::vector<int> gpus_;
   std::vector<int64_t> elemSize_;
   std::vector<std::string> names_;
@@ -441,7 +441,29 @@ private:
   // run instead of handing a torn-down transport to the GPU
   std::string poisoned_;
   void poison(const std::string &why);
-  void init_rccl(const std::function<bool(int, int)> &sharedDev); // realize(): communicator or staged fallback
+  // realize() in stages, in this order: each reads the configuration and what earlier stages decided
+  void resolve_backend_and_self_test();
+  void select_gpus();
+  void place();
+  void check_boundary_conditions() const; // dtype and thickness refusals
+  void create_local_domains();
+  void probe_ipc();
+  void gather_shared_devices();
+  void plan_messages();
+  void create_host_transports();
+  void create_device_transports(); // the steps below, in this order
+  void create_device_contexts();
+  void init_rccl(); // communicator or staged fallback
+  void build_local_translates();
+  void create_pipes();
+  void allocate_channel_buffers();
+  void ipc_handshake();
+  void build_channel_lists();
+  void finish_plan(double createStart); // createStart: when the transport stages began (timeCreate_)
+  // same-process copies without the directions crossing skipAxes, into list `slot` of the device contexts
+  // (0: translate / pipePack[0] / pipeUnpack[0], realize(); 1: translateSkip / pipe*[1], prepare_skip_wrapped)
+  void build_translates(int slot, int skipAxes);
+  void build_pipe_segs(int slot, int skipAxes);
   // Completion::IpcEvent: consume the last two exchanges' Acks so a later domain on the same group starts clean.
   // Polls at most timeout_s seconds and returns false if they did not all arrive; timeout_s <= 0 uses the group's
   // blocking receive (bounded by its own wait timeout).

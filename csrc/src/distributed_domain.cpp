@@ -5,18 +5,9 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <deque>
 #include <fstream>
 #include <functional>
-#include <set>
 #include <sstream>
-#include <thread>
 
 #include "stencil/comm/rccl_comm.hpp"
 #include "stencil/comm/tags.hpp"
@@ -134,21 +125,7 @@ DistributedDomain::~DistributedDomain() {
     if (c.ownData) (void)hipFree(c.ownData);
   }
   for (auto &d : I.devs) {
-    d.translate.release();
-    d.translateSkip.release();
-    d.coloPack.release();
-    d.coloPackLocal.release();
-    for (int k = 0; k < 2; ++k) {
-      d.pipePack[k].release();
-      d.pipeUnpack[k].release();
-    }
-    if (d.syncCounter) (void)hipFree(d.syncCounter);
-    if (d.xlog) (void)hipFree(d.xlog);
-    d.coloUnpack.release();
-    d.rcclPack.release();
-    d.rcclUnpack.release();
-    d.stagedPack.release();
-    d.stagedUnpack.release();
+    d.release();
     if (d.nccl) {
       if (poisoned_.empty())
         rccl::destroy(d.nccl);
@@ -172,7 +149,12 @@ int64_t DistributedDomain::add_data(int64_t elemSize, const std::string &name, D
 // ------------------------------------------------------------------------------------------------
 // RCCL communicator (or the host-staged fallback)
 // ------------------------------------------------------------------------------------------------
-void DistributedDomain::init_rccl(const std::function<bool(int, int)> &sharedDev) {
+// RCCL communicator over all (rank, device) pairs, created only if some rank needs it. An init error on any
+// rank (or TransportOptions::failRcclInit) is agreed on collectively and every RCCL channel falls back to the
+// host-staged transport (the reference's ladder also ends at the MPI path, src/stencil.cu:185-194).
+// Reads I.chans, I.devs and I.sharedDev; leaves the communicators, ncclPeer and I.rccl, or the fallback in I.chans,
+// plan_ and flags_.
+void DistributedDomain::init_rccl() {
   Impl &I = *impl_;
   comm::ProcGroup &pg = *pg_;
   const int myRank = pg.rank();
@@ -182,14 +164,11 @@ void DistributedDomain::init_rccl(const std::function<bool(int, int)> &sharedDev
   TraceRange trr("rccl init");
   // members: every (rank, device) whose GPU no other rank drives (pairs touching a shared GPU are staged)
   const int nLocal = int(I.devs.size());
-  std::vector<int> counts(size_t(pg.size()));
-  pg.allgather(&nLocal, sizeof(int), counts.data());
-  int maxN = 0;
-  for (int c : counts) maxN = std::max(maxN, c);
-  std::vector<int> padded(size_t(maxN), -1), allDevs(size_t(maxN) * size_t(pg.size()));
+  std::vector<int> counts, mine(size_t(nLocal), -1);
   for (int k = 0; k < nLocal; ++k)
-    if (!sharedDev(myRank, I.devs[size_t(k)].dev)) padded[size_t(k)] = I.devs[size_t(k)].dev;
-  pg.allgather(padded.data(), sizeof(int) * size_t(maxN), allDevs.data());
+    if (!I.shared_dev(myRank, I.devs[size_t(k)].dev)) mine[size_t(k)] = I.devs[size_t(k)].dev;
+  const std::vector<int> allDevs = allgather_padded(pg, mine, -1, &counts);
+  const int maxN = int(allDevs.size()) / pg.size();
   // RCCL rank of (rank r, slot k) = number of members before it
   std::vector<int> ncclRankOf(allDevs.size(), -1);
   int total = 0, root = -1;
@@ -282,32 +261,52 @@ void DistributedDomain::init_rccl(const std::function<bool(int, int)> &sharedDev
     if (c.method == MethodFlags::Rccl) c.method = MethodFlags::Staged;
   for (auto &e : plan_)
     if (e.method == MethodFlags::Rccl) e.method = MethodFlags::Staged;
-  flags_ = MethodFlags((int(flags_) & ~int(MethodFlags::Rccl)) | int(MethodFlags::Staged));
+  flags_ = without(flags_, MethodFlags::Rccl) | MethodFlags::Staged;
 }
 
 // ------------------------------------------------------------------------------------------------
 // realize
 // ------------------------------------------------------------------------------------------------
+// setup timers (reference STENCIL_SETUP_STATS, stencil.cu:31-538): max over ranks, or local and collective-free
+// when the option is compiled out
+static double setup_time(comm::ProcGroup &pg, double local) {
+  return STENCIL_SETUP_STATS ? pg.allreduce_max(local) : local;
+}
+
+// The stages below run in this order on every rank, in lock-step: each holds its process-group calls and its device
+// allocations in a fixed order, so neither may move between stages or inside one.
 void DistributedDomain::realize() {
   STENCIL_REQUIRE(!realized_, "realize() called twice");
   STENCIL_REQUIRE(!elemSize_.empty(), "add_data() before realize()");
   TraceRange tr0("DistributedDomain::realize");
-  Impl &I = *impl_;
-  comm::ProcGroup &pg = *pg_;
-  const int myRank = pg.rank();
-  // setup timers (reference STENCIL_SETUP_STATS, stencil.cu:31-538): max over ranks, or local and collective-free
-  // when the option is compiled out
-  auto setup_time = [&](double local) { return STENCIL_SETUP_STATS ? pg.allreduce_max(local) : local; };
+  resolve_backend_and_self_test();
+  select_gpus();
+  place();
+  create_local_domains();
+  probe_ipc();
+  gather_shared_devices();
+  plan_messages();
+  const double t0 = now_s();
+  TraceRange trc("DistributedDomain::realize: create");
+  if (backend_ == Backend::Device)
+    create_device_transports();
+  else
+    create_host_transports();
+  finish_plan(t0);
+}
 
+// Reads backendSet_, selfTest_ and flags_; leaves backend_, flags_ narrowed to the set that passed the self-test, and
+// selfTestReport_.
+void DistributedDomain::resolve_backend_and_self_test() {
+  comm::ProcGroup &pg = *pg_;
   if (!backendSet_) backend_ = gpu_topo::device_count() > 0 ? Backend::Device : Backend::Host;
-  const bool dev = backend_ == Backend::Device;
   if (selfTest_ && pg.size() > 1) {
     // ladder: as configured -> without Colocated -> without Rccl (host-staged); the last rung always runs
     TraceRange trs("transport self-test");
     std::vector<MethodFlags> ladder{flags_};
-    if (flags_ && MethodFlags::Colocated) ladder.push_back(MethodFlags(int(ladder.back()) & ~int(MethodFlags::Colocated)));
+    if (flags_ && MethodFlags::Colocated) ladder.push_back(without(ladder.back(), MethodFlags::Colocated));
     if (ladder.back() && MethodFlags::Rccl)
-      ladder.push_back(MethodFlags((int(ladder.back()) & ~int(MethodFlags::Rccl)) | int(MethodFlags::Staged)));
+      ladder.push_back(without(ladder.back(), MethodFlags::Rccl) | MethodFlags::Staged);
     std::ostringstream rep;
     bool found = false;
     for (size_t k = 0; k < ladder.size() && !found; ++k) {
@@ -319,16 +318,22 @@ void DistributedDomain::realize() {
       }
     }
     selfTestReport_ = rep.str();
-    if (myRank == 0) LOG_INFO("transport self-test: " << selfTestReport_);
+    if (pg.rank() == 0) LOG_INFO("transport self-test: " << selfTestReport_);
     STENCIL_REQUIRE(found, "no transport set passed the self-test: " << selfTestReport_);
   }
-  if (dev) STENCIL_REQUIRE(gpu_topo::device_count() > 0, "Device backend requested but no GPU is visible");
+  if (backend_ == Backend::Device)
+    STENCIL_REQUIRE(gpu_topo::device_count() > 0, "Device backend requested but no GPU is visible");
+}
 
-  // ---- node topology / GPU selection (reference stencil.hpp:158-245) ----
+// node topology / GPU selection (reference stencil.hpp:158-245). Reads backend_ and gpus_ as configured; leaves
+// gpus_, peer access among them, numaNode_ and the three topology timers.
+void DistributedDomain::select_gpus() {
+  comm::ProcGroup &pg = *pg_;
+  const bool dev = backend_ == Backend::Device;
   double t0 = now_s();
   const int coloSize = pg.colocated_size();
   const int coloRank = pg.colocated_rank();
-  timeMpiTopo_ = setup_time(now_s() - t0);
+  timeMpiTopo_ = setup_time(pg, now_s() - t0);
   t0 = now_s();
   if (gpus_.empty()) {
     if (dev) {
@@ -343,14 +348,14 @@ void DistributedDomain::realize() {
       gpus_ = {0};
     }
   }
-  timeNodeGpus_ = setup_time(now_s() - t0);
+  timeNodeGpus_ = setup_time(pg, now_s() - t0);
   t0 = now_s();
   if (dev) {
     for (int a : gpus_)
       for (int b : gpus_)
         if (a != b) gpu_topo::enable_peer(a, b);
   }
-  timePeerEn_ = setup_time(now_s() - t0);
+  timePeerEn_ = setup_time(pg, now_s() - t0);
   if (dev && topt_.numaAffinity) {
     int node = -2;
     for (int g : gpus_) {
@@ -359,30 +364,36 @@ void DistributedDomain::realize() {
     }
     if (node >= 0 && gpu_topo::bind_thread_to_numa(node)) {
       numaNode_ = node;
-      LOG_DEBUG("rank " << myRank << " bound to NUMA node " << node << " of its GPU(s)");
+      LOG_DEBUG("rank " << pg.rank() << " bound to NUMA node " << node << " of its GPU(s)");
     }
   }
+}
 
-  // ---- placement ----
-  t0 = now_s();
+// Reads gpus_, the radius and the placement options; leaves placement_ and timePlacement_, then refuses boundary
+// conditions the placement cannot serve.
+void DistributedDomain::place() {
+  const double t0 = now_s();
   {
     TraceRange tr("placement");
     if (strategy_ == PlacementStrategy::NodeAware) {
-      BandwidthFn bw = dev ? BandwidthFn([](int a, int b) { return gpu_topo::bandwidth(a, b); })
-                           : BandwidthFn([](int a, int b) { return a == b ? 10.0 : 1.0; });
-      placement_.reset(new NodeAwarePlacement(size_, pg, radius_, gpus_, bw, axisCost_, objective_));
+      BandwidthFn bw = backend_ == Backend::Device ? BandwidthFn([](int a, int b) { return gpu_topo::bandwidth(a, b); })
+                                                   : BandwidthFn([](int a, int b) { return a == b ? 10.0 : 1.0; });
+      placement_.reset(new NodeAwarePlacement(size_, *pg_, radius_, gpus_, bw, axisCost_, objective_));
     } else {
-      placement_.reset(new TrivialPlacement(size_, pg, gpus_));
+      placement_.reset(new TrivialPlacement(size_, *pg_, gpus_));
     }
   }
-  timePlacement_ = setup_time(now_s() - t0);
+  timePlacement_ = setup_time(*pg_, now_s() - t0);
   check_boundary_conditions();
+}
 
-  // ---- local domains ----
-  t0 = now_s();
+// Reads placement_ and the layout options; leaves domains_ realized (one per entry of gpus_) and timeRealize_.
+void DistributedDomain::create_local_domains() {
+  const double t0 = now_s();
+  const bool dev = backend_ == Backend::Device;
   domains_.reserve(gpus_.size());
   for (size_t di = 0; di < gpus_.size(); ++di) {
-    const Dim3 idx = placement_->get_idx(myRank, int(di));
+    const Dim3 idx = placement_->get_idx(rank(), int(di));
     const int device = placement_->get_device(idx);
     domains_.emplace_back(placement_->subdomain_size(idx), placement_->subdomain_origin(idx), dev ? device : -1, backend_);
     LocalDomain &d = domains_.back();
@@ -393,122 +404,79 @@ void DistributedDomain::realize() {
     d.set_interior_align(interiorAlign_);
     d.set_row_pad_lines(rowPadLines_);
     for (size_t q = 0; q < elemSize_.size(); ++q) d.add_data(elemSize_[q], names_[q], dtypes_[q]);
-    LOG_INFO("rank " << myRank << " domain " << di << " idx " << idx << " size " << d.size() << " origin " << d.origin()
+    LOG_INFO("rank " << rank() << " domain " << di << " idx " << idx << " size " << d.size() << " origin " << d.origin()
                      << " device " << device);
   }
   for (auto &d : domains_) d.realize();
-  timeRealize_ = setup_time(now_s() - t0);
+  timeRealize_ = setup_time(*pg_, now_s() - t0);
+}
 
-  // ---- HIP-IPC pre-flight: every rank maps a small uncached block of every co-located rank and reads it back.
-  // If any mapping fails anywhere, Colocated is disabled on all ranks (they then agree on RCCL/staged). ----
-  if (dev && any_methods(MethodFlags::Colocated) && pg.size() > 1 && pg.colocated_size() > 1 && topt_.ipcProbe) {
-    TraceRange trp("ipc probe");
-    // up to 3 collective attempts with a growing pause between them (50, 200 ms): a transient open/map failure on a
-    // busy node must not cost the transport. Every failed attempt logs the call that failed on this rank.
-    bool allOk = false;
-    for (int attempt = 0; attempt < 3 && !allOk; ++attempt) {
-      if (attempt > 0) std::this_thread::sleep_for(std::chrono::milliseconds(50 * (1 << (2 * (attempt - 1)))));
-      int ok = 1;
-      const char *failed = "";
-      int failedPeer = -1;
-      char *blk = nullptr;
-      HIP_CHECK(hipSetDevice(gpus_[0]));
-      if (hipExtMallocWithFlags((void **)&blk, 256, hipDeviceMallocUncached) != hipSuccess) {
-        (void)hipGetLastError();
-        ok = 0;
-        failed = "hipExtMallocWithFlags(uncached)";
-      }
-      hipIpcMemHandle_t mine{};
-      if (ok && hipIpcGetMemHandle(&mine, blk) != hipSuccess) {
-        (void)hipGetLastError();
-        ok = 0;
-        failed = "hipIpcGetMemHandle";
-      }
-      if (ok) {
-        const uint64_t tag = 0x57e9c11000000000ull + uint64_t(myRank);
-        HIP_CHECK(hipMemcpy(blk, &tag, sizeof(tag), hipMemcpyHostToDevice));
-      }
-      std::vector<hipIpcMemHandle_t> all(pg.size());
-      pg.allgather(&mine, sizeof(mine), all.data());
-      std::vector<int> oks(pg.size());
-      pg.allgather(&ok, sizeof(int), oks.data());
-      for (int r = 0; r < pg.size() && ok; ++r) {
-        if (r == myRank || !pg.colocated(r) || !oks[r]) continue;
-        char *peer = nullptr;
-        if (hipIpcOpenMemHandle((void **)&peer, all[r], hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
-          (void)hipGetLastError();
-          ok = 0;
-          failed = "hipIpcOpenMemHandle";
-          failedPeer = r;
-          break;
-        }
-        uint64_t got = 0;
-        if (hipMemcpy(&got, peer, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess ||
-            got != 0x57e9c11000000000ull + uint64_t(r)) {
-          (void)hipGetLastError();
-          ok = 0;
-          failed = "readback of the mapped block";
-          failedPeer = r;
-        }
-        (void)hipIpcCloseMemHandle(peer);
-      }
-      if (topt_.failIpcProbe) { // rehearses the fallback (tests)
-        ok = 0;
-        failed = "STENCIL_IPC_PROBE_FAIL";
-      }
-      if (!ok)
-        LOG_INFO("IPC pre-flight attempt " << attempt + 1 << "/3 failed on rank " << myRank << ": " << failed
-                                           << (failedPeer >= 0 ? " (peer rank " + std::to_string(failedPeer) + ")" : ""));
-      allOk = pg.allreduce_min_i64(ok) == 1;
-      pg.barrier(); // peers are done with our block
-      if (blk) (void)hipFree(blk);
-    }
-    if (!allOk) {
-      if (myRank == 0) LOG_WARN("HIP IPC between co-located ranks is unavailable; Colocated transport disabled");
-      flags_ = MethodFlags(int(flags_) & ~int(MethodFlags::Colocated));
-    }
-  }
-
-  // ---- physical device identity of every (rank, device ordinal): ranks may number devices differently, and RCCL
-  // refuses a communicator in which two ranks drive one GPU. Pairs with an endpoint on a GPU that another rank of
-  // the same host also drives never use RCCL (select_method); everything else keeps its transport. ----
-  std::map<std::pair<int, int>, bool> sharedDev; // (rank, ordinal) -> GPU driven by another rank too
-  if (dev && pg.size() > 1) {
-    int nmine = int(gpus_.size()), maxN = 0;
-    std::vector<int> counts(pg.size());
-    pg.allgather(&nmine, sizeof(int), counts.data());
-    for (int c : counts) maxN = std::max(maxN, c);
-    struct DevId {
-      int64_t ordinal;
-      uint64_t bus;
-    };
-    std::vector<DevId> mine(size_t(maxN), DevId{-1, 0}), all(size_t(maxN) * pg.size());
-    for (int k = 0; k < nmine; ++k) {
-      char bus[64] = {0};
-      HIP_CHECK(hipDeviceGetPCIBusId(bus, sizeof(bus), gpus_[size_t(k)]));
-      mine[size_t(k)] = DevId{gpus_[size_t(k)], uint64_t(std::hash<std::string>()(std::string(bus)))};
-    }
-    pg.allgather(mine.data(), sizeof(DevId) * size_t(maxN), all.data());
-    for (int r = 0; r < pg.size(); ++r)
-      for (int k = 0; k < counts[r]; ++k) {
-        const DevId &a = all[size_t(r) * maxN + k];
-        bool sh = false;
-        for (int r2 = 0; r2 < pg.size() && !sh; ++r2) {
-          if (r2 == r || pg.hostname(r2) != pg.hostname(r)) continue;
-          for (int k2 = 0; k2 < counts[r2]; ++k2) sh |= all[size_t(r2) * maxN + k2].bus == a.bus;
-        }
-        sharedDev[{r, int(a.ordinal)}] = sh;
-      }
-  }
-  auto shared_dev = [&](int r, int ordinal) {
-    auto it = sharedDev.find({r, ordinal});
-    return it != sharedDev.end() && it->second;
+// physical device identity of every (rank, device ordinal): ranks may number devices differently, and RCCL
+// refuses a communicator in which two ranks drive one GPU. Pairs with an endpoint on a GPU that another rank of
+// the same host also drives never use RCCL (select_method); everything else keeps its transport.
+// Reads gpus_; leaves Impl::sharedDev (empty on the host backend and on one rank).
+void DistributedDomain::gather_shared_devices() {
+  comm::ProcGroup &pg = *pg_;
+  if (backend_ != Backend::Device || pg.size() == 1) return;
+  struct DevId {
+    int64_t ordinal;
+    uint64_t bus;
   };
+  std::vector<DevId> mine;
+  for (int g : gpus_) {
+    char bus[64] = {0};
+    HIP_CHECK(hipDeviceGetPCIBusId(bus, sizeof(bus), g));
+    mine.push_back(DevId{g, uint64_t(std::hash<std::string>()(std::string(bus)))});
+  }
+  std::vector<int> counts;
+  const std::vector<DevId> all = allgather_padded(pg, mine, DevId{-1, 0}, &counts);
+  const size_t maxN = all.size() / size_t(pg.size());
+  for (int r = 0; r < pg.size(); ++r)
+    for (int k = 0; k < counts[size_t(r)]; ++k) {
+      const DevId &a = all[size_t(r) * maxN + size_t(k)];
+      bool sh = false;
+      for (int r2 = 0; r2 < pg.size() && !sh; ++r2) {
+        if (r2 == r || pg.hostname(r2) != pg.hostname(r)) continue;
+        for (int k2 = 0; k2 < counts[size_t(r2)]; ++k2) sh |= all[size_t(r2) * maxN + size_t(k2)].bus == a.bus;
+      }
+      impl_->sharedDev[{r, int(a.ordinal)}] = sh;
+    }
+}
 
-  // ---- plan messages (reference src/stencil.cu:132-239) ----
-  t0 = now_s();
-  const Dim3 gdim = placement_->dim();
+// the channel of (method, direction, local sub-domain, remote sub-domain), appended to `chans` on first use
+static Channel &channel_for(std::vector<Channel> &chans, const Placement &pl, MethodFlags m, bool send, int localDom,
+                            const Dim3 &localIdx, const Dim3 &remoteIdx) {
+  for (Channel &c : chans)
+    if (c.method == m && c.send == send && c.localDom == localDom && c.remoteIdx == remoteIdx) return c;
+  const Dim3 gdim = pl.dim();
   const int64_t numSub = gdim.flatten();
+  Channel c;
+  c.method = m;
+  c.send = send;
+  c.localDom = localDom;
+  c.localIdx = localIdx;
+  c.remoteIdx = remoteIdx;
+  c.remoteRank = pl.get_rank(remoteIdx);
+  c.remoteId = pl.get_subdomain_id(remoteIdx);
+  c.remoteDev = pl.get_device(remoteIdx);
+  c.localDev = pl.get_device(localIdx);
+  // order key and tag name the (source, destination) pair of sub-domains: the same on both ends of the channel
+  const int64_t sl = linearize(send ? localIdx : remoteIdx, gdim), dl = linearize(send ? remoteIdx : localIdx, gdim);
+  c.orderKey = sl * numSub + dl;
+  c.tag = comm::make_tag(comm::MsgKind::Data, sl, dl, numSub);
+  chans.push_back(c);
+  return chans.back();
+}
+
+// plan messages (reference src/stencil.cu:132-239). Reads placement_, domains_, flags_ and Impl::sharedDev; leaves
+// plan_, remoteHalo_, I.chans (messages sorted, bytes set), I.localTranslates, I.pipeMsgs and timePlan_.
+void DistributedDomain::plan_messages() {
+  Impl &I = *impl_;
+  comm::ProcGroup &pg = *pg_;
+  const int myRank = pg.rank();
+  const bool dev = backend_ == Backend::Device;
+  const double t0 = now_s();
+  const Dim3 gdim = placement_->dim();
   auto can_access = [&](int a, int b) {
     if (a == b) return true;
     int can = 0;
@@ -529,7 +497,7 @@ void DistributedDomain::realize() {
     if (dev) {
       pi.peer = sameRank && gpu_topo::peer(srcDev, dstDev);
       pi.canAccess = !sameRank && pi.sameHost && (any_methods(MethodFlags::Colocated)) && can_access(srcDev, dstDev);
-      pi.sharedGpu = !sameRank && (shared_dev(srcRank, srcDev) || shared_dev(dstRank, dstDev));
+      pi.sharedGpu = !sameRank && (I.shared_dev(srcRank, srcDev) || I.shared_dev(dstRank, dstDev));
     }
     const MethodFlags m = select_method(flags_, pi);
     if (m == MethodFlags::Staged && pi.sharedGpu && any_methods(MethodFlags::Rccl) && !warnedShared) {
@@ -540,10 +508,6 @@ void DistributedDomain::realize() {
     return m;
   };
 
-  // channel maps: (method, localDom, remoteLinear) -> channel index
-  std::map<std::tuple<int, int, int64_t>, int> sendKey, recvKey;
-  std::vector<std::tuple<int, int, Dim3>> localTranslates; // (srcDom, dstDom, dir)
-  std::map<std::pair<int, int>, std::vector<Message>> pipeMsgs; // PeerCopy over DMA engines: (srcDom, dstDom) -> msgs
   plan_.clear();
   remoteHalo_.assign(domains_.size(), std::array<uint8_t, 27>{});
   for (size_t di = 0; di < domains_.size(); ++di) {
@@ -562,36 +526,12 @@ void DistributedDomain::realize() {
         int64_t bytes = 0;
         for (int64_t q = 0; q < domains_[di].num_data(); ++q) bytes += domains_[di].halo_bytes(-dir, q);
         plan_.push_back({m, myIdx, dstIdx, myRank, dstRank, myDev, dstDev, dir, bytes});
-        if (m == MethodFlags::PeerCopy && topt_.peerCopy == TransportOptions::Copy::Engine && dstId != int(di) && dev) {
-          pipeMsgs[{int(di), dstId}].push_back(Message{dir, int(di), dstId});
-        } else if (m == MethodFlags::Kernel || m == MethodFlags::PeerCopy) {
-          localTranslates.emplace_back(int(di), dstId, dir);
-        } else {
-          const auto key = std::make_tuple(int(m), int(di), linearize(dstIdx, gdim));
-          auto it = sendKey.find(key);
-          int ci;
-          if (it == sendKey.end()) {
-            ci = int(I.chans.size());
-            sendKey[key] = ci;
-            Channel c;
-            c.method = m;
-            c.send = true;
-            c.localDom = int(di);
-            c.localIdx = myIdx;
-            c.remoteIdx = dstIdx;
-            c.remoteRank = dstRank;
-            c.remoteId = dstId;
-            c.remoteDev = dstDev;
-            c.localDev = myDev;
-            const int64_t sl = linearize(myIdx, gdim), dl = linearize(dstIdx, gdim);
-            c.orderKey = sl * numSub + dl;
-            c.tag = comm::make_tag(comm::MsgKind::Data, sl, dl, numSub);
-            I.chans.push_back(c);
-          } else {
-            ci = it->second;
-          }
-          I.chans[ci].msgs.push_back(Message{dir, int(di), dstId});
-        }
+        if (m == MethodFlags::PeerCopy && topt_.peerCopy == TransportOptions::Copy::Engine && dstId != int(di) && dev)
+          I.pipeMsgs[{int(di), dstId}].push_back(Message{dir, int(di), dstId});
+        else if (m == MethodFlags::Kernel || m == MethodFlags::PeerCopy)
+          I.localTranslates.emplace_back(int(di), dstId, dir);
+        else
+          channel_for(I.chans, *placement_, m, true, int(di), myIdx, dstIdx).msgs.push_back(Message{dir, int(di), dstId});
       }
       // recv
       if (boundary_.reachable(myIdx, -dir, gdim)) {
@@ -603,30 +543,7 @@ void DistributedDomain::realize() {
         // the halo on side -dir is valid after the same-device translate only for Kernel messages
         if (m != MethodFlags::Kernel) remoteHalo_[di][size_t(dir_index(-dir))] = 1;
         if (m == MethodFlags::Kernel || m == MethodFlags::PeerCopy) continue; // written by the sender directly
-        const auto key = std::make_tuple(int(m), int(di), linearize(srcIdx, gdim));
-        auto it = recvKey.find(key);
-        int ci;
-        if (it == recvKey.end()) {
-          ci = int(I.chans.size());
-          recvKey[key] = ci;
-          Channel c;
-          c.method = m;
-          c.send = false;
-          c.localDom = int(di);
-          c.localIdx = myIdx;
-          c.remoteIdx = srcIdx;
-          c.remoteRank = srcRank;
-          c.remoteId = srcId;
-          c.remoteDev = srcDev;
-          c.localDev = myDev;
-          const int64_t sl = linearize(srcIdx, gdim), dl = linearize(myIdx, gdim);
-          c.orderKey = sl * numSub + dl;
-          c.tag = comm::make_tag(comm::MsgKind::Data, sl, dl, numSub);
-          I.chans.push_back(c);
-        } else {
-          ci = it->second;
-        }
-        I.chans[ci].msgs.push_back(Message{dir, srcId, int(di)});
+        channel_for(I.chans, *placement_, m, false, int(di), myIdx, srcIdx).msgs.push_back(Message{dir, srcId, int(di)});
       }
     }
   }
@@ -634,267 +551,307 @@ void DistributedDomain::realize() {
     std::sort(c.msgs.begin(), c.msgs.end());
     c.bytes = packed_size(domains_[c.localDom], c.msgs);
   }
-  timePlan_ = setup_time(now_s() - t0);
+  timePlan_ = setup_time(pg, now_s() - t0);
+}
 
-  // ---- create transports ----
-  t0 = now_s();
-  TraceRange trc("DistributedDomain::realize: create");
-  if (!dev) {
-    // host backend: translate + staged only, all executed on the host
-    for (const auto &t : localTranslates) {
-      const LocalDomain &s = domains_[std::get<0>(t)], &d = domains_[std::get<1>(t)];
-      for (int p = 0; p < 2; ++p)
-        build_translate(s, d, std::get<2>(t), p == 0, I.hostTranslate.host[p], topt_.xFaceSectors);
+// pack (send channels) or unpack segments of the channels `cis` into variant parity * slots + slot of `out`, against
+// the buffer buf(channel, slot) (reference wire layout: messages sorted by dir, each quantity aligned to its element
+// size, reference packer.cuh:136-160)
+template <typename BufFn>
+static void build_channel_segs(const std::vector<LocalDomain> &doms, std::vector<Channel> &chans,
+                               const std::vector<int> &cis, SegList &out, int slots, BufFn buf) {
+  for (int ci : cis) {
+    Channel &c = chans[size_t(ci)];
+    for (int p = 0; p < 2; ++p)
+      for (int slot = 0; slot < slots; ++slot)
+        (c.send ? build_pack_segs : build_unpack_segs)(doms[size_t(c.localDom)], c.msgs, buf(c, slot), p == 0,
+                                                       out.host[p * slots + slot]);
+  }
+}
+// the channel's own buffer of `bytes`: dbuf on the device, hostBuf on the host backend
+static char *staging_buffer(Channel &c, int) { return c.dbuf ? c.dbuf : c.hostBuf.data(); }
+
+// host backend: translate + staged only, all executed on the host. Reads I.localTranslates and I.chans; leaves the
+// channels' host buffers and the three host segment lists.
+void DistributedDomain::create_host_transports() {
+  Impl &I = *impl_;
+  for (const auto &t : I.localTranslates) {
+    const LocalDomain &s = domains_[std::get<0>(t)], &d = domains_[std::get<1>(t)];
+    for (int p = 0; p < 2; ++p)
+      build_translate_segs(s, d, std::get<2>(t), p == 0, I.hostTranslate.host[p], topt_.xFaceSectors);
+  }
+  for (int ci = 0; ci < int(I.chans.size()); ++ci) {
+    Channel &c = I.chans[size_t(ci)];
+    STENCIL_REQUIRE(c.method == MethodFlags::Staged, "host backend supports only Kernel/Staged transports");
+    c.hostBuf.resize(size_t(std::max<int64_t>(c.bytes, 1)));
+    build_channel_segs(domains_, I.chans, {ci}, c.send ? I.hostStagedPack : I.hostStagedUnpack, 1, staging_buffer);
+  }
+  I.hostTranslate.upload(-1);
+  I.hostStagedPack.upload(-1);
+  I.hostStagedUnpack.upload(-1);
+}
+
+// device backend. Reads domains_, I.chans, I.localTranslates, I.pipeMsgs and I.sharedDev; every step reads what the
+// steps before it left in Impl.
+void DistributedDomain::create_device_transports() {
+  create_device_contexts();
+  init_rccl();
+  build_local_translates();
+  create_pipes();
+  allocate_channel_buffers();
+  ipc_handshake();
+  build_channel_lists();
+}
+
+// Leaves one DevCtx per distinct local device (stream, events, its sub-domains), the ready events per sub-domain and
+// the host-mapped error and done words.
+void DistributedDomain::create_device_contexts() {
+  Impl &I = *impl_;
+  for (size_t di = 0; di < domains_.size(); ++di) {
+    const int d = domains_[di].gpu();
+    if (!I.devIndex.count(d)) {
+      I.devIndex[d] = int(I.devs.size());
+      I.devs.emplace_back();
+      DevCtx &c = I.devs.back();
+      c.dev = d;
+      c.comm = Stream(d, Priority::HIGH);
+      c.done = Event(d);
+      c.translated = Event(d);
+      if (!I.callerDone) I.callerDone = Event(d);
+    }
+    I.devs[I.devIndex[d]].doms.push_back(int(di));
+    I.ready.emplace_back(d);
+    I.readyPending.push_back(false);
+  }
+  HIP_CHECK(hipHostMalloc((void **)&I.errHost, sizeof(int), hipHostMallocMapped));
+  *I.errHost = 0;
+  HIP_CHECK(hipHostGetDevicePointer((void **)&I.errDev, I.errHost, 0));
+  HIP_CHECK(hipHostMalloc((void **)&I.doneHost, sizeof(uint64_t) * I.devs.size(), hipHostMallocMapped));
+  for (size_t k = 0; k < I.devs.size(); ++k) I.doneHost[k] = 0;
+  HIP_CHECK(hipHostGetDevicePointer((void **)&I.doneDev, I.doneHost, 0));
+  I.nullReady = Event(I.devs[0].dev);
+}
+
+void DistributedDomain::build_translates(int slot, int skipAxes) {
+  Impl &I = *impl_;
+  for (const auto &t : I.localTranslates) {
+    const Dim3 dir = std::get<2>(t);
+    if (crosses(dir, skipAxes)) continue;
+    const LocalDomain &s = domains_[std::get<0>(t)], &d = domains_[std::get<1>(t)];
+    DevCtx &ctx = I.devs[I.devIndex[s.gpu()]];
+    SegList &list = slot == 0 ? ctx.translate : ctx.translateSkip;
+    for (int p = 0; p < 2; ++p) build_translate_segs(s, d, dir, p == 0, list.host[p], x_face_lines(s, d));
+  }
+}
+
+// same-process direct stores; x faces as whole lines where asked for or where their lines outgrow the cache.
+// Reads I.localTranslates; leaves I.xLineDevs, the translate lists (uploaded with the channel lists) and peerWriters.
+void DistributedDomain::build_local_translates() {
+  Impl &I = *impl_;
+  std::map<int, int64_t> xLineBytes;
+  for (const auto &t : I.localTranslates) {
+    const LocalDomain &s = domains_[std::get<0>(t)], &d = domains_[std::get<1>(t)];
+    const Dim3 dir = std::get<2>(t);
+    if (dir.x != 0 && dir.y == 0 && dir.z == 0 && s.gpu() == d.gpu())
+      xLineBytes[s.gpu()] += s.size().y * s.size().z * s.num_data() * 192;
+    if (d.gpu() != s.gpu()) I.devs[I.devIndex[d.gpu()]].peerWriters.insert(s.gpu());
+  }
+  for (auto &kv : xLineBytes)
+    if (topt_.xFaceSectors || (topt_.xFaceLinesAutoBytes > 0 && kv.second >= topt_.xFaceLinesAutoBytes))
+      I.xLineDevs.insert(kv.first);
+  if (!I.xLineDevs.empty() && !topt_.xFaceSectors)
+    LOG_DEBUG("x faces as whole lines (auto) on " << I.xLineDevs.size() << " device(s)");
+  build_translates(0, 0);
+}
+
+void DistributedDomain::build_pipe_segs(int slot, int skipAxes) {
+  Impl &I = *impl_;
+  for (auto &pp : I.pipes) {
+    std::vector<Message> keep;
+    for (const Message &m : pp.msgs)
+      if (!crosses(m.dir, skipAxes)) keep.push_back(m);
+    pp.bytes[slot] = keep.empty() ? 0 : packed_size(domains_[size_t(pp.srcDom)], keep);
+    if (keep.empty()) continue;
+    DevCtx &sc = I.devs[size_t(I.devIndex[pp.srcDev])];
+    DevCtx &dc = I.devs[size_t(I.devIndex[pp.dstDev])];
+    for (int p = 0; p < 2; ++p) {
+      build_pack_segs(domains_[size_t(pp.srcDom)], keep, pp.sbuf, p == 0, sc.pipePack[slot].host[p]);
+      build_unpack_segs(domains_[size_t(pp.dstDom)], keep, pp.rbuf, p == 0, dc.pipeUnpack[slot].host[p]);
+    }
+  }
+}
+
+// Reads I.pipeMsgs; leaves I.pipes with their buffers and the pipe lists [0] uploaded, then per device the pipe
+// events, sharedGpu and the zeroed block counters.
+void DistributedDomain::create_pipes() {
+  Impl &I = *impl_;
+  for (auto &kv : I.pipeMsgs) {
+    PeerPipe pp;
+    pp.srcDom = kv.first.first;
+    pp.dstDom = kv.first.second;
+    pp.srcDev = domains_[size_t(pp.srcDom)].gpu();
+    pp.dstDev = domains_[size_t(pp.dstDom)].gpu();
+    pp.msgs = kv.second;
+    std::sort(pp.msgs.begin(), pp.msgs.end());
+    pp.bytes[0] = pp.bytes[1] = packed_size(domains_[size_t(pp.srcDom)], pp.msgs);
+    const size_t nb = size_t(std::max<int64_t>(pp.bytes[0], 1));
+    HIP_CHECK(hipSetDevice(pp.srcDev));
+    HIP_CHECK(hipMalloc(&pp.sbuf, nb));
+    HIP_CHECK(hipSetDevice(pp.dstDev));
+    HIP_CHECK(hipMalloc(&pp.rbuf, nb));
+    const int k = int(I.pipes.size());
+    I.devs[size_t(I.devIndex[pp.srcDev])].pipesOut.push_back(k);
+    I.devs[size_t(I.devIndex[pp.dstDev])].pipesIn.push_back(k);
+    I.pipes.push_back(std::move(pp));
+  }
+  build_pipe_segs(0, 0);
+  for (auto &ctx : I.devs) {
+    ctx.sharedGpu = I.shared_dev(rank(), ctx.dev);
+    ctx.pipePack[0].upload(ctx.dev);
+    ctx.pipeUnpack[0].upload(ctx.dev);
+    if (!ctx.pipesOut.empty()) ctx.pipeSent = Event(ctx.dev);
+    if (!ctx.pipesIn.empty()) ctx.pipeUnpacked = Event(ctx.dev);
+    HIP_CHECK(hipSetDevice(ctx.dev));
+    HIP_CHECK(hipMalloc(&ctx.syncCounter, 2 * sizeof(uint32_t)));
+    HIP_CHECK(hipMemset(ctx.syncCounter, 0, 2 * sizeof(uint32_t)));
+  }
+  // copy streams for DMA-engine copies are created on first use (forked_copies): every stream can take a hardware
+  // queue, and ranks that share a GPU slow down by orders of magnitude once their queues oversubscribe the
+  // device (profiles/r3/cliff/)
+}
+
+// Reads I.chans (method, bytes); leaves every channel's device and pinned buffers and the per-device channel index
+// lists, and the devices synchronized (the memsets have landed before a handle leaves the process).
+void DistributedDomain::allocate_channel_buffers() {
+  Impl &I = *impl_;
+  for (int ci = 0; ci < int(I.chans.size()); ++ci) {
+    Channel &c = I.chans[ci];
+    DevCtx &ctx = I.devs[I.devIndex[c.localDev]];
+    HIP_CHECK(hipSetDevice(c.localDev));
+    const size_t nb = size_t(std::max<int64_t>(c.bytes, 1));
+    if (c.method == MethodFlags::Staged) {
+      HIP_CHECK(hipMalloc(&c.dbuf, nb));
+      // pinned on the GPU's NUMA node when realize() bound this thread there (pages follow the thread's policy)
+      HIP_CHECK(hipHostMalloc((void **)&c.hbuf, nb, numaNode_ >= 0 ? hipHostMallocNumaUser : hipHostMallocDefault));
+      (c.send ? ctx.stagedSend : ctx.stagedRecv).push_back(ci);
+    } else if (c.method == MethodFlags::Rccl) {
+      HIP_CHECK(hipMalloc(&c.dbuf, nb));
+      (c.send ? ctx.rcclSend : ctx.rcclRecv).push_back(ci);
+    } else if (c.method == MethodFlags::Colocated) {
+      // flag words (arrival on the receiver, credit on the sender) in uncached memory: polled across processes
+      // and GPUs, written remotely
+      HIP_CHECK(hipExtMallocWithFlags((void **)&c.ownFlag, 256, hipDeviceMallocUncached));
+      HIP_CHECK(hipMemset(c.ownFlag, 0, 256));
+      c.slotStride = round_up(int64_t(nb), 256);
+      if (!c.send) {
+        const size_t dataBytes = size_t(2 * c.slotStride);
+        switch (topt_.inbox) {
+        case TransportOptions::Inbox::Uncached:
+          HIP_CHECK(hipExtMallocWithFlags((void **)&c.ownData, dataBytes, hipDeviceMallocUncached));
+          break;
+        case TransportOptions::Inbox::Fine:
+          HIP_CHECK(hipExtMallocWithFlags((void **)&c.ownData, dataBytes, hipDeviceMallocFinegrained));
+          break;
+        case TransportOptions::Inbox::Coarse:
+          HIP_CHECK(hipMalloc((void **)&c.ownData, dataBytes));
+          break;
+        }
+        HIP_CHECK(hipMemset(c.ownData, 0, dataBytes));
+      } else {
+        HIP_CHECK(hipMalloc(&c.dbuf, nb)); // Engine copies: the packed message before the DMA copy
+      }
+      (c.send ? ctx.coloSend : ctx.coloRecv).push_back(ci);
+    }
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+}
+
+// IPC handshake for colocated channels: every side sends its handles first (non-blocking), then receives.
+// receiver -> sender: {arrival flag block, data block}; sender -> receiver: {credit flag block}.
+// Reads the Colocated channels' own blocks; leaves their remote mappings and, with Completion::IpcEvent, their
+// interprocess events. Ends with a barrier.
+void DistributedDomain::ipc_handshake() {
+  Impl &I = *impl_;
+  comm::ProcGroup &pg = *pg_;
+  TraceRange tri("ipc handshake");
+  for (auto &c : I.chans) {
+    if (c.method != MethodFlags::Colocated) continue;
+    hipIpcMemHandle_t h[2] = {};
+    HIP_CHECK(hipSetDevice(c.localDev));
+    HIP_CHECK(hipIpcGetMemHandle(&h[0], c.ownFlag));
+    if (!c.send) HIP_CHECK(hipIpcGetMemHandle(&h[1], c.ownData));
+    pg.send(c.remoteRank, retag(c.tag, c.send ? comm::MsgKind::IpcCredit : comm::MsgKind::IpcInbox), h,
+            c.send ? sizeof(h[0]) : sizeof(h));
+  }
+  for (auto &c : I.chans) {
+    if (c.method != MethodFlags::Colocated) continue;
+    hipIpcMemHandle_t h[2] = {};
+    // a sender needs the receiver's flag + data blocks, a receiver the sender's credit block
+    pg.recv(c.remoteRank, retag(c.tag, c.send ? comm::MsgKind::IpcInbox : comm::MsgKind::IpcCredit), h,
+            c.send ? sizeof(h) : sizeof(h[0]));
+    HIP_CHECK(hipSetDevice(c.localDev));
+    HIP_CHECK(hipIpcOpenMemHandle((void **)&c.remoteFlag, h[0], hipIpcMemLazyEnablePeerAccess));
+    if (c.send) HIP_CHECK(hipIpcOpenMemHandle((void **)&c.remoteData, h[1], hipIpcMemLazyEnablePeerAccess));
+  }
+  // Completion::IpcEvent: sender -> receiver, the handle of the sender's interprocess event per channel
+  if (topt_.completion == TransportOptions::Completion::IpcEvent) {
+    for (auto &c : I.chans) {
+      if (c.method != MethodFlags::Colocated || !c.send) continue;
+      HIP_CHECK(hipSetDevice(c.localDev));
+      HIP_CHECK(hipEventCreateWithFlags(&c.ipcEvent, hipEventDisableTiming | hipEventInterprocess));
+      hipIpcEventHandle_t h{};
+      HIP_CHECK(hipIpcGetEventHandle(&h, c.ipcEvent));
+      pg.send(c.remoteRank, retag(c.tag, comm::MsgKind::IpcEvent), &h, sizeof(h));
     }
     for (auto &c : I.chans) {
-      STENCIL_REQUIRE(c.method == MethodFlags::Staged, "host backend supports only Kernel/Staged transports");
-      c.hostBuf.resize(size_t(std::max<int64_t>(c.bytes, 1)));
-      for (int p = 0; p < 2; ++p) {
-        if (c.send)
-          build_pack(domains_[c.localDom], c.msgs, c.hostBuf.data(), p == 0, I.hostStagedPack.host[p]);
-        else
-          build_unpack(domains_[c.localDom], c.msgs, c.hostBuf.data(), p == 0, I.hostStagedUnpack.host[p]);
-      }
-    }
-    I.hostTranslate.upload(-1);
-    I.hostStagedPack.upload(-1);
-    I.hostStagedUnpack.upload(-1);
-  } else {
-    // per-device contexts
-    for (size_t di = 0; di < domains_.size(); ++di) {
-      const int d = domains_[di].gpu();
-      if (!I.devIndex.count(d)) {
-        I.devIndex[d] = int(I.devs.size());
-        I.devs.emplace_back();
-        DevCtx &c = I.devs.back();
-        c.dev = d;
-        c.comm = Stream(d, Priority::HIGH);
-        c.done = Event(d);
-        c.translated = Event(d);
-        if (!I.callerDone) I.callerDone = Event(d);
-      }
-      I.devs[I.devIndex[d]].doms.push_back(int(di));
-      I.ready.emplace_back(d);
-      I.readyPending.push_back(false);
-    }
-    HIP_CHECK(hipHostMalloc((void **)&I.errHost, sizeof(int), hipHostMallocMapped));
-    *I.errHost = 0;
-    HIP_CHECK(hipHostGetDevicePointer((void **)&I.errDev, I.errHost, 0));
-    HIP_CHECK(hipHostMalloc((void **)&I.doneHost, sizeof(uint64_t) * I.devs.size(), hipHostMallocMapped));
-    for (size_t k = 0; k < I.devs.size(); ++k) I.doneHost[k] = 0;
-    HIP_CHECK(hipHostGetDevicePointer((void **)&I.doneDev, I.doneHost, 0));
-    I.nullReady = Event(I.devs[0].dev);
-
-    // RCCL communicator over all (rank, device) pairs, created only if some rank needs it. An init error on any
-    // rank (or TransportOptions::failRcclInit) is agreed on collectively and every RCCL channel falls back to the
-    // host-staged transport (the reference's ladder also ends at the MPI path, src/stencil.cu:185-194).
-    init_rccl(shared_dev);
-
-    // same-process direct stores; x faces as whole lines where asked for or where their lines outgrow the cache
-    I.localTranslates = localTranslates;
-    {
-      std::map<int, int64_t> xLineBytes;
-      for (const auto &t : localTranslates) {
-        const LocalDomain &s = domains_[std::get<0>(t)];
-        const Dim3 dir = std::get<2>(t);
-        if (dir.x != 0 && dir.y == 0 && dir.z == 0 && s.gpu() == domains_[std::get<1>(t)].gpu())
-          xLineBytes[s.gpu()] += s.size().y * s.size().z * s.num_data() * 192;
-      }
-      for (auto &kv : xLineBytes)
-        if (topt_.xFaceSectors || (topt_.xFaceLinesAutoBytes > 0 && kv.second >= topt_.xFaceLinesAutoBytes))
-          I.xLineDevs.insert(kv.first);
-      if (!I.xLineDevs.empty() && !topt_.xFaceSectors)
-        LOG_DEBUG("x faces as whole lines (auto) on " << I.xLineDevs.size() << " device(s)");
-    }
-    for (const auto &t : localTranslates) {
-      const LocalDomain &s = domains_[std::get<0>(t)], &d = domains_[std::get<1>(t)];
-      DevCtx &ctx = I.devs[I.devIndex[s.gpu()]];
-      const bool lines = x_face_lines(s, d);
-      for (int p = 0; p < 2; ++p) build_translate(s, d, std::get<2>(t), p == 0, ctx.translate.host[p], lines);
-      if (d.gpu() != s.gpu()) I.devs[I.devIndex[d.gpu()]].peerWriters.insert(s.gpu());
-    }
-    for (auto &kv : pipeMsgs) {
-      PeerPipe pp;
-      pp.srcDom = kv.first.first;
-      pp.dstDom = kv.first.second;
-      pp.srcDev = domains_[size_t(pp.srcDom)].gpu();
-      pp.dstDev = domains_[size_t(pp.dstDom)].gpu();
-      pp.msgs = kv.second;
-      std::sort(pp.msgs.begin(), pp.msgs.end());
-      pp.bytes[0] = pp.bytes[1] = packed_size(domains_[size_t(pp.srcDom)], pp.msgs);
-      const size_t nb = size_t(std::max<int64_t>(pp.bytes[0], 1));
-      HIP_CHECK(hipSetDevice(pp.srcDev));
-      HIP_CHECK(hipMalloc(&pp.sbuf, nb));
-      HIP_CHECK(hipSetDevice(pp.dstDev));
-      HIP_CHECK(hipMalloc(&pp.rbuf, nb));
-      const int k = int(I.pipes.size());
-      DevCtx &sc = I.devs[size_t(I.devIndex[pp.srcDev])];
-      DevCtx &dc = I.devs[size_t(I.devIndex[pp.dstDev])];
-      sc.pipesOut.push_back(k);
-      dc.pipesIn.push_back(k);
-      for (int p = 0; p < 2; ++p) {
-        build_pack(domains_[size_t(pp.srcDom)], pp.msgs, pp.sbuf, p == 0, sc.pipePack[0].host[p]);
-        build_unpack(domains_[size_t(pp.dstDom)], pp.msgs, pp.rbuf, p == 0, dc.pipeUnpack[0].host[p]);
-      }
-      I.pipes.push_back(std::move(pp));
-    }
-    for (auto &ctx : I.devs) {
-      ctx.sharedGpu = shared_dev(myRank, ctx.dev);
-      ctx.pipePack[0].upload(ctx.dev);
-      ctx.pipeUnpack[0].upload(ctx.dev);
-      if (!ctx.pipesOut.empty()) ctx.pipeSent = Event(ctx.dev);
-      if (!ctx.pipesIn.empty()) ctx.pipeUnpacked = Event(ctx.dev);
-      HIP_CHECK(hipSetDevice(ctx.dev));
-      HIP_CHECK(hipMalloc(&ctx.syncCounter, 2 * sizeof(uint32_t)));
-      HIP_CHECK(hipMemset(ctx.syncCounter, 0, 2 * sizeof(uint32_t)));
-    }
-    // copy streams for DMA-engine copies are created on first use (forked_copies): every stream can take a hardware
-    // queue, and ranks that share a GPU slow down by orders of magnitude once their queues oversubscribe the
-    // device (profiles/r3/cliff/)
-
-    // channel buffers
-    for (int ci = 0; ci < int(I.chans.size()); ++ci) {
-      Channel &c = I.chans[ci];
-      DevCtx &ctx = I.devs[I.devIndex[c.localDev]];
+      if (c.method != MethodFlags::Colocated || c.send) continue;
+      hipIpcEventHandle_t h{};
+      pg.recv(c.remoteRank, retag(c.tag, comm::MsgKind::IpcEvent), &h, sizeof(h));
       HIP_CHECK(hipSetDevice(c.localDev));
-      const size_t nb = size_t(std::max<int64_t>(c.bytes, 1));
-      if (c.method == MethodFlags::Staged) {
-        HIP_CHECK(hipMalloc(&c.dbuf, nb));
-        // pinned on the GPU's NUMA node when realize() bound this thread there (pages follow the thread's policy)
-        HIP_CHECK(hipHostMalloc((void **)&c.hbuf, nb, numaNode_ >= 0 ? hipHostMallocNumaUser : hipHostMallocDefault));
-        (c.send ? ctx.stagedSend : ctx.stagedRecv).push_back(ci);
-      } else if (c.method == MethodFlags::Rccl) {
-        HIP_CHECK(hipMalloc(&c.dbuf, nb));
-        (c.send ? ctx.rcclSend : ctx.rcclRecv).push_back(ci);
-      } else if (c.method == MethodFlags::Colocated) {
-        // flag words (arrival on the receiver, credit on the sender) in uncached memory: polled across processes
-        // and GPUs, written remotely
-        HIP_CHECK(hipExtMallocWithFlags((void **)&c.ownFlag, 256, hipDeviceMallocUncached));
-        HIP_CHECK(hipMemset(c.ownFlag, 0, 256));
-        c.slotStride = round_up(int64_t(nb), 256);
-        if (!c.send) {
-          const size_t dataBytes = size_t(2 * c.slotStride);
-          switch (topt_.inbox) {
-          case TransportOptions::Inbox::Uncached:
-            HIP_CHECK(hipExtMallocWithFlags((void **)&c.ownData, dataBytes, hipDeviceMallocUncached));
-            break;
-          case TransportOptions::Inbox::Fine:
-            HIP_CHECK(hipExtMallocWithFlags((void **)&c.ownData, dataBytes, hipDeviceMallocFinegrained));
-            break;
-          case TransportOptions::Inbox::Coarse:
-            HIP_CHECK(hipMalloc((void **)&c.ownData, dataBytes));
-            break;
-          }
-          HIP_CHECK(hipMemset(c.ownData, 0, dataBytes));
-        } else {
-          HIP_CHECK(hipMalloc(&c.dbuf, nb)); // Engine copies: the packed message before the DMA copy
-        }
-        (c.send ? ctx.coloSend : ctx.coloRecv).push_back(ci);
-      }
+      HIP_CHECK(hipIpcOpenEventHandle(&c.ipcEvent, h));
     }
-    HIP_CHECK(hipDeviceSynchronize());
-
-    // IPC handshake for colocated channels: every side sends its handles first (non-blocking), then receives.
-    // receiver -> sender: {arrival flag block, data block}; sender -> receiver: {credit flag block}
-    {
-      TraceRange tri("ipc handshake");
-      for (auto &c : I.chans) {
-        if (c.method != MethodFlags::Colocated) continue;
-        hipIpcMemHandle_t h[2] = {};
-        HIP_CHECK(hipSetDevice(c.localDev));
-        HIP_CHECK(hipIpcGetMemHandle(&h[0], c.ownFlag));
-        if (!c.send) HIP_CHECK(hipIpcGetMemHandle(&h[1], c.ownData));
-        pg.send(c.remoteRank, retag(c.tag, c.send ? comm::MsgKind::IpcCredit : comm::MsgKind::IpcInbox), h,
-                c.send ? sizeof(h[0]) : sizeof(h));
-      }
-      for (auto &c : I.chans) {
-        if (c.method != MethodFlags::Colocated) continue;
-        hipIpcMemHandle_t h[2] = {};
-        // a sender needs the receiver's flag + data blocks, a receiver the sender's credit block
-        pg.recv(c.remoteRank, retag(c.tag, c.send ? comm::MsgKind::IpcInbox : comm::MsgKind::IpcCredit), h,
-                c.send ? sizeof(h) : sizeof(h[0]));
-        HIP_CHECK(hipSetDevice(c.localDev));
-        HIP_CHECK(hipIpcOpenMemHandle((void **)&c.remoteFlag, h[0], hipIpcMemLazyEnablePeerAccess));
-        if (c.send) HIP_CHECK(hipIpcOpenMemHandle((void **)&c.remoteData, h[1], hipIpcMemLazyEnablePeerAccess));
-      }
-      // Completion::IpcEvent: sender -> receiver, the handle of the sender's interprocess event per channel
-      if (topt_.completion == TransportOptions::Completion::IpcEvent) {
-        for (auto &c : I.chans) {
-          if (c.method != MethodFlags::Colocated || !c.send) continue;
-          HIP_CHECK(hipSetDevice(c.localDev));
-          HIP_CHECK(hipEventCreateWithFlags(&c.ipcEvent, hipEventDisableTiming | hipEventInterprocess));
-          hipIpcEventHandle_t h{};
-          HIP_CHECK(hipIpcGetEventHandle(&h, c.ipcEvent));
-          pg.send(c.remoteRank, retag(c.tag, comm::MsgKind::IpcEvent), &h, sizeof(h));
-        }
-        for (auto &c : I.chans) {
-          if (c.method != MethodFlags::Colocated || c.send) continue;
-          hipIpcEventHandle_t h{};
-          pg.recv(c.remoteRank, retag(c.tag, comm::MsgKind::IpcEvent), &h, sizeof(h));
-          HIP_CHECK(hipSetDevice(c.localDev));
-          HIP_CHECK(hipIpcOpenEventHandle(&c.ipcEvent, h));
-        }
-        I.ipcEvents = true;
-        I.ipcEventFirstEpoch = 1;
-      }
-      pg.barrier();
-    }
-
-    // segment lists per device
-    for (auto &ctx : I.devs) {
-      for (int ci : ctx.coloSend) {
-        Channel &c = I.chans[ci];
-        const LocalDomain &dom = domains_[c.localDom];
-        for (int p = 0; p < 2; ++p) {
-          for (int slot = 0; slot < 2; ++slot)
-            build_pack(dom, c.msgs, c.remoteData + slot * c.slotStride, p == 0, ctx.coloPack.host[p * 2 + slot]);
-          build_pack(dom, c.msgs, c.dbuf, p == 0, ctx.coloPackLocal.host[p]);
-        }
-      }
-      for (int ci : ctx.coloRecv) {
-        Channel &c = I.chans[ci];
-        const LocalDomain &dom = domains_[c.localDom];
-        for (int p = 0; p < 2; ++p)
-          for (int slot = 0; slot < 2; ++slot)
-            build_unpack(dom, c.msgs, c.ownData + slot * c.slotStride, p == 0, ctx.coloUnpack.host[p * 2 + slot]);
-      }
-      for (int ci : ctx.rcclSend)
-        for (int p = 0; p < 2; ++p)
-          build_pack(domains_[I.chans[ci].localDom], I.chans[ci].msgs, I.chans[ci].dbuf, p == 0, ctx.rcclPack.host[p]);
-      for (int ci : ctx.rcclRecv)
-        for (int p = 0; p < 2; ++p)
-          build_unpack(domains_[I.chans[ci].localDom], I.chans[ci].msgs, I.chans[ci].dbuf, p == 0, ctx.rcclUnpack.host[p]);
-      for (int ci : ctx.stagedSend)
-        for (int p = 0; p < 2; ++p)
-          build_pack(domains_[I.chans[ci].localDom], I.chans[ci].msgs, I.chans[ci].dbuf, p == 0, ctx.stagedPack.host[p]);
-      for (int ci : ctx.stagedRecv)
-        for (int p = 0; p < 2; ++p)
-          build_unpack(domains_[I.chans[ci].localDom], I.chans[ci].msgs, I.chans[ci].dbuf, p == 0,
-                       ctx.stagedUnpack.host[p]);
-      ctx.translate.upload(ctx.dev);
-      ctx.coloPack.upload(ctx.dev);
-      ctx.coloPackLocal.upload(ctx.dev);
-      ctx.coloUnpack.upload(ctx.dev);
-      ctx.rcclPack.upload(ctx.dev);
-      ctx.rcclUnpack.upload(ctx.dev);
-      ctx.stagedPack.upload(ctx.dev);
-      ctx.stagedUnpack.upload(ctx.dev);
-      // RCCL matching order: canonical (src, dst) sub-domain order on both sides of every pair
-      auto byKey = [&](int a, int b) { return I.chans[a].orderKey < I.chans[b].orderKey; };
-      std::sort(ctx.rcclSend.begin(), ctx.rcclSend.end(), byKey);
-      std::sort(ctx.rcclRecv.begin(), ctx.rcclRecv.end(), byKey);
-    }
-
+    I.ipcEvents = true;
+    I.ipcEventFirstEpoch = 1;
   }
-  // bytes per method (after any RCCL -> staged fallback) and the plan file
+  pg.barrier();
+}
+
+// segment lists per device. Reads the channels' buffers and mappings; leaves every channel list and the translate
+// list uploaded, and the RCCL channels in matching order.
+void DistributedDomain::build_channel_lists() {
+  Impl &I = *impl_;
+  // a Colocated sender packs into the receiver's mapped inbox slots (or, for engine copies, its own staging buffer), and
+  // the receiver unpacks its own slots
+  auto remote_slot = [](Channel &c, int slot) { return c.remoteData + slot * c.slotStride; };
+  auto own_slot = [](Channel &c, int slot) { return c.ownData + slot * c.slotStride; };
+  for (auto &ctx : I.devs) {
+    build_channel_segs(domains_, I.chans, ctx.coloSend, ctx.coloPack, 2, remote_slot);
+    build_channel_segs(domains_, I.chans, ctx.coloSend, ctx.coloPackLocal, 1, staging_buffer);
+    build_channel_segs(domains_, I.chans, ctx.coloRecv, ctx.coloUnpack, 2, own_slot);
+    build_channel_segs(domains_, I.chans, ctx.rcclSend, ctx.rcclPack, 1, staging_buffer);
+    build_channel_segs(domains_, I.chans, ctx.rcclRecv, ctx.rcclUnpack, 1, staging_buffer);
+    build_channel_segs(domains_, I.chans, ctx.stagedSend, ctx.stagedPack, 1, staging_buffer);
+    build_channel_segs(domains_, I.chans, ctx.stagedRecv, ctx.stagedUnpack, 1, staging_buffer);
+    ctx.upload();
+    // RCCL matching order: canonical (src, dst) sub-domain order on both sides of every pair
+    auto byKey = [&](int a, int b) { return I.chans[a].orderKey < I.chans[b].orderKey; };
+    std::sort(ctx.rcclSend.begin(), ctx.rcclSend.end(), byKey);
+    std::sort(ctx.rcclRecv.begin(), ctx.rcclRecv.end(), byKey);
+  }
+}
+
+// bytes per method (after any RCCL -> staged fallback) and the plan file. Leaves bytesPerMethod_, timeCreate_ (the
+// transports, from createStart) and realized_; ends with a barrier.
+void DistributedDomain::finish_plan(double createStart) {
+  comm::ProcGroup &pg = *pg_;
   bytesPerMethod_ = {};
   for (const auto &e : plan_) bytesPerMethod_[size_t(method_slot(e.method))] += uint64_t(e.bytes);
   for (int m = 0; m < 5; ++m) bytesPerMethod_[size_t(m)] = pg.allreduce_sum_u64(bytesPerMethod_[size_t(m)]);
   if (!planPrefix_.empty()) {
-    std::ofstream f(planPrefix_ + "_" + std::to_string(myRank) + ".txt");
+    std::ofstream f(planPrefix_ + "_" + std::to_string(pg.rank()) + ".txt");
     f << plan_summary();
   }
-  timeCreate_ = setup_time(now_s() - t0);
+  timeCreate_ = setup_time(pg, now_s() - createStart);
   realized_ = true;
   pg.barrier();
 }

@@ -304,45 +304,15 @@ void DistributedDomain::prepare_skip_wrapped(int axes) {
                   "axes " << axes << " are not self-periodic (self_wrap_axes = " << self_wrap_axes() << ")");
   Impl &I = *impl_;
   if (axes == I.skipAxes || backend_ == Backend::Host) return;
-  for (auto &ctx : I.devs) {
-    ctx.translateSkip.release();
-    ctx.translateSkip = SegList();
-  }
-  for (const auto &t : I.localTranslates) {
-    const Dim3 dir = std::get<2>(t);
-    if (((axes & 1) && dir.x != 0) || ((axes & 2) && dir.y != 0) || ((axes & 4) && dir.z != 0)) continue;
-    const LocalDomain &sd = domains_[std::get<0>(t)], &dd = domains_[std::get<1>(t)];
-    DevCtx &ctx = I.devs[I.devIndex[sd.gpu()]];
-    for (int p = 0; p < 2; ++p) build_translate(sd, dd, dir, p == 0, ctx.translateSkip.host[p], x_face_lines(sd, dd));
-  }
-  for (auto &ctx : I.devs) ctx.translateSkip.upload(ctx.dev);
-  // PeerCopy pipes: the same subset, packed compactly
-  for (auto &ctx : I.devs) {
-    ctx.pipePack[1].release();
-    ctx.pipePack[1] = SegList();
-    ctx.pipeUnpack[1].release();
-    ctx.pipeUnpack[1] = SegList();
-  }
-  for (auto &pp : I.pipes) {
-    std::vector<Message> keep;
-    for (const Message &mm : pp.msgs) {
-      const Dim3 dir = mm.dir;
-      if (((axes & 1) && dir.x != 0) || ((axes & 2) && dir.y != 0) || ((axes & 4) && dir.z != 0)) continue;
-      keep.push_back(mm);
+  for (auto &ctx : I.devs)
+    for (SegList *l : {&ctx.translateSkip, &ctx.pipePack[1], &ctx.pipeUnpack[1]}) {
+      l->release();
+      *l = SegList();
     }
-    pp.bytes[1] = keep.empty() ? 0 : packed_size(domains_[size_t(pp.srcDom)], keep);
-    if (keep.empty()) continue;
-    DevCtx &sc = I.devs[size_t(I.devIndex[pp.srcDev])];
-    DevCtx &dc = I.devs[size_t(I.devIndex[pp.dstDev])];
-    for (int p = 0; p < 2; ++p) {
-      build_pack(domains_[size_t(pp.srcDom)], keep, pp.sbuf, p == 0, sc.pipePack[1].host[p]);
-      build_unpack(domains_[size_t(pp.dstDom)], keep, pp.rbuf, p == 0, dc.pipeUnpack[1].host[p]);
-    }
-  }
-  for (auto &ctx : I.devs) {
-    ctx.pipePack[1].upload(ctx.dev);
-    ctx.pipeUnpack[1].upload(ctx.dev);
-  }
+  build_translates(1, axes);
+  build_pipe_segs(1, axes); // PeerCopy pipes: the same subset, packed compactly
+  for (auto &ctx : I.devs)
+    for (SegList *l : {&ctx.translateSkip, &ctx.pipePack[1], &ctx.pipeUnpack[1]}) l->upload(ctx.dev);
   I.skipAxes = axes;
 }
 

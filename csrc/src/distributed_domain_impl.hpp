@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <chrono>
 #include <deque>
 #include <map>
@@ -168,6 +169,22 @@ struct DevCtx {
   SegList rcclPack, rcclUnpack;   // variant = parity
   SegList stagedPack, stagedUnpack;
   rccl::Comm nccl = nullptr;
+  // the lists realize() completes last. pipePack[0] / pipeUnpack[0] are uploaded where the pipes are built, and
+  // translateSkip, pipePack[1] and pipeUnpack[1] by prepare_skip_wrapped.
+  void upload() {
+    for (SegList *l : {&translate, &coloPack, &coloPackLocal, &coloUnpack, &rcclPack, &rcclUnpack, &stagedPack,
+                       &stagedUnpack})
+      l->upload(dev);
+  }
+  // every device allocation of the context but the communicator (the owner destroys or aborts that one afterwards)
+  void release() {
+    for (SegList *l : {&translate, &translateSkip, &coloPack, &coloPackLocal, &pipePack[0], &pipeUnpack[0], &pipePack[1],
+                       &pipeUnpack[1]})
+      l->release();
+    if (syncCounter) (void)hipFree(syncCounter);
+    if (xlog) (void)hipFree(xlog);
+    for (SegList *l : {&coloUnpack, &rcclPack, &rcclUnpack, &stagedPack, &stagedUnpack}) l->release();
+  }
 };
 
 struct DistributedDomain::Impl {
@@ -185,7 +202,14 @@ struct DistributedDomain::Impl {
   // host backend
   SegList hostTranslate, hostStagedPack, hostStagedUnpack;
   bool rccl = false;
+  // realize(): (rank, device ordinal) -> the GPU is driven by another rank of the same host too
+  std::map<std::pair<int, int>, bool> sharedDev;
+  bool shared_dev(int rank, int ordinal) const {
+    auto it = sharedDev.find({rank, ordinal});
+    return it != sharedDev.end() && it->second;
+  }
   std::vector<std::tuple<int, int, Dim3>> localTranslates; // (srcDom, dstDom, dir) of the Kernel/PeerCopy messages
+  std::map<std::pair<int, int>, std::vector<Message>> pipeMsgs; // PeerCopy over DMA engines: (srcDom, dstDom) -> msgs
   std::vector<PeerPipe> pipes;                               // PeerCopy messages over DMA engines (see PeerPipe)
   int skipAxes = 0;                                         // axes translateSkip leaves out (0 = not prepared)
   // exchanges enqueued on a caller stream (single device) vs on the comm stream: each kind waits for the last
@@ -206,21 +230,24 @@ struct DistributedDomain::Impl {
 };
 
 
-// ------------------------------------------------------------------------------------------------
-// segment builders (reference wire layout: messages sorted by dir, each quantity aligned to its element size,
-// reference packer.cuh:136-160)
-// ------------------------------------------------------------------------------------------------
-inline void build_pack(const LocalDomain &dom, const std::vector<Message> &msgs, char *buf, bool curr,
-                       std::vector<CopySeg> &out) {
-  build_pack_segs(dom, msgs, buf, curr, out);
+// direction `dir` crosses one of `axes` (mask 1 = x, 2 = y, 4 = z)
+inline bool crosses(const Dim3 &dir, int axes) {
+  return ((axes & 1) && dir.x != 0) || ((axes & 2) && dir.y != 0) || ((axes & 4) && dir.z != 0);
 }
-inline void build_unpack(const LocalDomain &dom, const std::vector<Message> &msgs, char *buf, bool curr,
-                         std::vector<CopySeg> &out) {
-  build_unpack_segs(dom, msgs, buf, curr, out);
-}
-inline void build_translate(const LocalDomain &src, const LocalDomain &dst, const Dim3 &dir, bool curr,
-                            std::vector<CopySeg> &out, bool xSectors = false) {
-  build_translate_segs(src, dst, dir, curr, out, xSectors);
+
+// every rank's list, each padded with `fill` to the longest one: rank r's element k at [r * (size / ranks) + k],
+// counts[r] its length. Two collectives: the lengths, then the padded lists.
+template <typename T>
+std::vector<T> allgather_padded(comm::ProcGroup &pg, std::vector<T> mine, const T &fill, std::vector<int> *counts) {
+  const int n = int(mine.size());
+  int maxN = 0;
+  counts->assign(size_t(pg.size()), 0);
+  pg.allgather(&n, sizeof(int), counts->data());
+  for (int c : *counts) maxN = std::max(maxN, c);
+  mine.resize(size_t(maxN), fill);
+  std::vector<T> all(size_t(maxN) * size_t(pg.size()));
+  pg.allgather(mine.data(), sizeof(T) * size_t(maxN), all.data());
+  return all;
 }
 
 } // namespace stencil

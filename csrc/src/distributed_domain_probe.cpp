@@ -1,15 +1,17 @@
-// DistributedDomain transport self-test: a coordinate-encoded probe domain run on a forked process group (split out
-// of distributed_domain.cpp; called from realize()).
+// DistributedDomain pre-flight probes, both called from realize(): the transport self-test (a coordinate-encoded
+// probe domain run on a forked process group) and the HIP-IPC mapping probe between co-located ranks.
 #include "stencil/domain/distributed_domain.hpp"
 
 #include <hip/hip_runtime_api.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "stencil/rt/hip_check.hpp"
@@ -113,6 +115,82 @@ int64_t DistributedDomain::probe_transports(MethodFlags m) {
     }
   } // the probe domain (and its bounded destructor barrier on the fork) is gone before the verdict
   return int64_t(pg_->allreduce_sum_u64(uint64_t(bad)));
+}
+
+// HIP-IPC pre-flight: every rank maps a small uncached block of every co-located rank and reads it back.
+// If any mapping fails anywhere, Colocated is disabled on all ranks (they then agree on RCCL/staged).
+// Reads gpus_, flags_ and the probe options; may drop Colocated from flags_.
+void DistributedDomain::probe_ipc() {
+  comm::ProcGroup &pg = *pg_;
+  const int myRank = pg.rank();
+  if (backend_ != Backend::Device || !any_methods(MethodFlags::Colocated) || pg.size() == 1 ||
+      pg.colocated_size() <= 1 || !topt_.ipcProbe)
+    return;
+  TraceRange trp("ipc probe");
+  // up to 3 collective attempts with a growing pause between them (50, 200 ms): a transient open/map failure on a
+  // busy node must not cost the transport. Every failed attempt logs the call that failed on this rank.
+  bool allOk = false;
+  for (int attempt = 0; attempt < 3 && !allOk; ++attempt) {
+    if (attempt > 0) std::this_thread::sleep_for(std::chrono::milliseconds(50 * (1 << (2 * (attempt - 1)))));
+    int ok = 1;
+    const char *failed = "";
+    int failedPeer = -1;
+    char *blk = nullptr;
+    HIP_CHECK(hipSetDevice(gpus_[0]));
+    if (hipExtMallocWithFlags((void **)&blk, 256, hipDeviceMallocUncached) != hipSuccess) {
+      (void)hipGetLastError();
+      ok = 0;
+      failed = "hipExtMallocWithFlags(uncached)";
+    }
+    hipIpcMemHandle_t mine{};
+    if (ok && hipIpcGetMemHandle(&mine, blk) != hipSuccess) {
+      (void)hipGetLastError();
+      ok = 0;
+      failed = "hipIpcGetMemHandle";
+    }
+    if (ok) {
+      const uint64_t tag = 0x57e9c11000000000ull + uint64_t(myRank);
+      HIP_CHECK(hipMemcpy(blk, &tag, sizeof(tag), hipMemcpyHostToDevice));
+    }
+    std::vector<hipIpcMemHandle_t> all(pg.size());
+    pg.allgather(&mine, sizeof(mine), all.data());
+    std::vector<int> oks(pg.size());
+    pg.allgather(&ok, sizeof(int), oks.data());
+    for (int r = 0; r < pg.size() && ok; ++r) {
+      if (r == myRank || !pg.colocated(r) || !oks[r]) continue;
+      char *peer = nullptr;
+      if (hipIpcOpenMemHandle((void **)&peer, all[r], hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
+        (void)hipGetLastError();
+        ok = 0;
+        failed = "hipIpcOpenMemHandle";
+        failedPeer = r;
+        break;
+      }
+      uint64_t got = 0;
+      if (hipMemcpy(&got, peer, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess ||
+          got != 0x57e9c11000000000ull + uint64_t(r)) {
+        (void)hipGetLastError();
+        ok = 0;
+        failed = "readback of the mapped block";
+        failedPeer = r;
+      }
+      (void)hipIpcCloseMemHandle(peer);
+    }
+    if (topt_.failIpcProbe) { // rehearses the fallback (tests)
+      ok = 0;
+      failed = "STENCIL_IPC_PROBE_FAIL";
+    }
+    if (!ok)
+      LOG_INFO("IPC pre-flight attempt " << attempt + 1 << "/3 failed on rank " << myRank << ": " << failed
+                                         << (failedPeer >= 0 ? " (peer rank " + std::to_string(failedPeer) + ")" : ""));
+    allOk = pg.allreduce_min_i64(ok) == 1;
+    pg.barrier(); // peers are done with our block
+    if (blk) (void)hipFree(blk);
+  }
+  if (!allOk) {
+    if (myRank == 0) LOG_WARN("HIP IPC between co-located ranks is unavailable; Colocated transport disabled");
+    flags_ = without(flags_, MethodFlags::Colocated);
+  }
 }
 
 } // namespace stencil

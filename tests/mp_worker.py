@@ -62,6 +62,29 @@ def scenario_exchange(backend, methods, radius_name, size):
     return bad
 
 
+def scenario_plan(backend, methods, radius_name, size):
+    """plan_cases.py: one exchange against the coordinate oracle (the plan is a working one), then this rank's
+    plan_summary() between markers"""
+    import plan_cases as cases
+    g = st.init_process_group()
+    radius = cases.radii(st)[radius_name]
+    dd = st.DistributedDomain(*size, group=g)
+    dd.set_backend(backend)
+    dd.set_transport_options(transport_from_env())
+    dd.set_radius(radius)
+    if backend == st.Backend.Device:
+        dd.set_gpus([0])
+    dd.set_methods(methods)
+    dd.set_plan_file("")
+    q = dd.add_data("c", torch.int64)
+    dd.realize()
+    fill_coords(dd, q)
+    dd.exchange()
+    bad = check_exchange(dd, q, radius)
+    print(f"rank {g.rank()} plan bad {bad}\n" + cases.BEGIN.format(g.rank()) + dd.plan_summary() + cases.END, flush=True)
+    return bad
+
+
 def scenario_exchange_types(backend, methods, radius_name, size):
     """Nine quantities of element sizes 1..24 B (named dtypes and opaque elements) against the byte oracle, 3 epochs
     with swap(): across ranks every element size goes through the packed transports (on the device: the fused wait +
@@ -404,6 +427,8 @@ def main():
         methods = methods | getattr(st.MethodFlags, name)
     if sc == "exchange":
         bad = scenario_exchange(backend, methods, sys.argv[2], tuple(int(v) for v in sys.argv[3].split(",")))
+    elif sc == "plan":
+        bad = scenario_plan(backend, methods, sys.argv[2], tuple(int(v) for v in sys.argv[3].split(",")))
     elif sc == "exchange_types":
         bad = scenario_exchange_types(backend, methods, sys.argv[2], tuple(int(v) for v in sys.argv[3].split(",")))
     elif sc == "canary":

@@ -64,7 +64,8 @@ int main(int argc, char **argv) {
   ArgParser p("7-point stencil kernel sweep on one GPU");
   p.option(&n, "--n", "cube edge").option(&iters, "--iters", "timed launches per config")
       .option(&reps, "--reps", "repetitions of the whole sweep (interleaved)")
-      .option(&only, "--only", "run only 'lds', 'reg', 'copy', 'star' (weighted stars of radius 1-3 beside stencil7) or 'reduce' (field "
+      .option(&only, "--only", "run only 'lds', 'reg', 'copy', 'star' (weighted stars of radius 1-3 beside stencil7), 'box' (27-point boxes beside "
+                             "stencil7 and the radius-1 star; 'boxzc': their z-chunk sweep) or 'reduce' (field "
                              "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange) or "
                              "'axpby' (field algebra beside the field reductions)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
@@ -381,6 +382,77 @@ int main(int argc, char **argv) {
         const double us = timeit([&] { stencil_star_apply(l3, 0, reg3, w, s, t); });
         std::printf("stencil_star,%d,2,%d,%.2f,%.1f,%.3f,path%d\n", r, li.zchunk, us, cells / us / 1e3,
                     cells * 8 / us / 1e6, li.path);
+      }
+    }
+  }
+  if (only == "box" || only == "boxzc") {
+    // weighted 27-point boxes (fp32 and fp64) on radius-(1, 1, 1) domains, interleaved per repetition with the default
+    // 7-point single step (variant 2) on the radius-1 domain and the radius-1 star on the box's domain: all read the
+    // field once and write it once. The one-thread-per-cell box kernel runs on an unpadded twin of each domain.
+    auto box_domain = [&](bool f64, bool pad) {
+      auto l = std::make_unique<LocalDomain>(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
+      l->set_radius(Radius::face_edge_corner(1, 1, 1));
+      l->set_padding(pad);
+      if (f64)
+        l->add_data<double>("d");
+      else
+        l->add_data<float>("d");
+      l->realize();
+      fill_value(*l, 0, 0.5, true, s);
+      s.sync();
+      return l;
+    };
+    BoxWeights bw; // the binomial filter (values do not matter)
+    for (int k = 0; k < 3; ++k)
+      for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i) bw.w[k][j][i] = double(1 << ((k == 1) + (j == 1) + (i == 1))) / 64.0;
+    StarWeights sw;
+    sw.radius = 1;
+    sw.center = 0.25;
+    for (int ax = 0; ax < 3; ++ax)
+      for (int sd = 0; sd < 2; ++sd) sw.w[ax][sd][0] = 0.125;
+    for (int f64 = 0; f64 < 2; ++f64) {
+      const double bytes = f64 ? 16 : 8;
+      const char *ty = f64 ? "fp64" : "fp32";
+      {
+        auto lb = box_domain(f64 != 0, true);
+        const Rect3 regb = lb->get_compute_region();
+        for (int rep = 0; rep < reps && only == "boxzc"; ++rep)
+          for (int zc : {0, 32, 43, 52, 64, 86, 128}) { // the z-chunk length (blocks per launch) around the automatic choice
+            StencilTune t;
+            t.zchunk = zc;
+            const BoxLaunchInfo li = stencil_box_launch_info(*lb, 0, regb, bw, t);
+            const double us = timeit([&] { stencil_box_apply(*lb, 0, regb, bw, s, t); });
+            std::printf("stencil_box,%s,2,%d,%.2f,%.1f,%.3f,blocks%lld\n", ty, li.zchunk, us, cells / us / 1e3,
+                        cells * bytes / us / 1e6, (long long)li.blocks);
+          }
+        for (int rep = 0; rep < reps && only == "box"; ++rep) {
+          StencilTune t;
+          if (!f64) {
+            const double us7 = timeit([&] { stencil7_apply(ld, 0, reg, StencilKind::Jacobi, sph, s, t); });
+            std::printf("stencil7,%d,%d,%d,%.2f,%.1f,%.3f,nw%d\n", t.variant, t.ty, t.zchunk, us7, cells / us7 / 1e3,
+                        cells * 8 / us7 / 1e6, t.nw);
+          }
+          const StarLaunchInfo si = stencil_star_launch_info(*lb, 0, regb, sw, t);
+          const double uss = timeit([&] { stencil_star_apply(*lb, 0, regb, sw, s, t); });
+          std::printf("stencil_star,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", ty, si.zchunk, uss, cells / uss / 1e3,
+                      cells * bytes / uss / 1e6, si.path);
+          const BoxLaunchInfo li = stencil_box_launch_info(*lb, 0, regb, bw, t);
+          const double us = timeit([&] { stencil_box_apply(*lb, 0, regb, bw, s, t); });
+          std::printf("stencil_box,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", ty, li.zchunk, us, cells / us / 1e3,
+                      cells * bytes / us / 1e6, li.path);
+        }
+      }
+      if (only == "box") {
+        auto lg = box_domain(f64 != 0, false);
+        const Rect3 regg = lg->get_compute_region();
+        for (int rep = 0; rep < reps; ++rep) {
+          StencilTune t;
+          const BoxLaunchInfo li = stencil_box_launch_info(*lg, 0, regg, bw, t);
+          const double us = timeit([&] { stencil_box_apply(*lg, 0, regg, bw, s, t); });
+          std::printf("stencil_box_unpadded,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", ty, li.zchunk, us, cells / us / 1e3,
+                      cells * bytes / us / 1e6, li.path);
+        }
       }
     }
   }

@@ -392,6 +392,41 @@ struct StarLaunchInfo {
 StarLaunchInfo stencil_star_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, const StarWeights &w,
                                         const StencilTune &tune = StencilTune());
 
+// Weighted 27-point box stencil (stencil_box.hip): for a quantity of element type T (fp32 / fp64)
+//   acc = w[-1][-1][-1] * u(c + (-1, -1, -1)); then for (dz, dy, dx) in lexicographic order, dz slowest, dx fastest:
+//   acc += w[dz][dy][dx] * u(c + (dx, dy, dz))
+// with the weights converted to T once on the host and every product and sum its own IEEE rounding in T in exactly
+// this order whatever direction a block marches in z (no FMA contraction; zero weights are multiplied like any other,
+// so NaN / Inf propagate). All 27 weights are independent. Bitwise equal to stencil2_amd.ops.box_step_reference.
+struct BoxWeights {
+  double w[3][3][3] = {}; // [dz + 1][dy + 1][dx + 1]
+};
+// an fp32 / fp64 quantity (or opaque 4- / 8-byte elements) and all 26 direction radii >= 1 (a 19-point user still needs
+// the corners exchanged: zero weights are multiplied, and an unexchanged corner may hold anything)
+bool stencil_box_supported(const LocalDomain &dom, int64_t qi);
+// next(region) = box(curr) for one quantity of one LocalDomain; only cells of `region` (global coordinates, inside
+// the compute region; empty: no-op) are written. Neighbours come from the face, edge and corner halos of curr
+// (exchange() first; Radius::face_edge_corner(1, 1, 1) suffices). Device sub-domains in the aligned vector layout (as
+// stencil7_apply's) run a 2.5D z-march: one 16-B x chunk of 2 rows per lane, every block marching upwards with three
+// partial sums per output cell in flight (the plane at z finishes out(z - 1), continues out(z) and starts out(z + 1),
+// so dz = -1 is summed first), each plane published to LDS once (the block's 16 rows plus one halo row each side) for
+// the row above and below a lane's own, x neighbours from adjacent lanes, fp32 sums as packed pairs, each source cell
+// read from HBM about once per sweep; any other layout runs one thread per cell, Backend::Host a plain loop. Of
+// `tune`: zchunk (0 = one round of resident blocks, at most two per CU, chunks of >= 16 planes), nontemporal and
+// xcdRemap; alternateZ is ignored (a downward march would sum dz = +1 first); tune.wrap != 0 is refused (no in-kernel
+// wrap, forwarding or temporal fusion).
+void stencil_box_apply(const LocalDomain &dom, int64_t qi, const Rect3 &region, const BoxWeights &w,
+                       hipStream_t stream, const StencilTune &tune = StencilTune());
+// What stencil_box_apply would run for these arguments (nothing is launched; the same refusals raise)
+struct BoxLaunchInfo {
+  int path = 0;       // -1 nothing (empty region), 0 host loop, 1 one thread per cell, 2 the z-march kernel
+  int zchunk = 0;     // z-march: planes per block
+  int zchunks = 0;    // z-march: chunks along z
+  int64_t blocks = 0; // z-march: blocks of the launch
+};
+BoxLaunchInfo stencil_box_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, const BoxWeights &w,
+                                      const StencilTune &tune = StencilTune());
+
 // Jacobi init: curr = 0.5 on `region` (reference bin/jacobi3d.cu:18-29)
 void jacobi_init(const LocalDomain &dom, int64_t qi, const Rect3 &region, hipStream_t stream);
 // Astaroth init: interior = sin(2*pi/period*(origin+x+y+z)) (x,y,z raw indices), halo = -10 (astaroth_sim.cu:14-61)

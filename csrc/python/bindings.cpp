@@ -1023,6 +1023,39 @@ PYBIND11_MODULE(_C, m) {
           return o;
         },
         py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("tune"));
+  py::class_<BoxWeights>(m, "BoxWeights")
+      .def(py::init<>())
+      .def("get", [](const BoxWeights &w, int dz, int dy, int dx) {
+        STENCIL_REQUIRE(dz >= -1 && dz <= 1 && dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1, "BoxWeights offset");
+        return w.w[dz + 1][dy + 1][dx + 1];
+      }, py::arg("dz"), py::arg("dy"), py::arg("dx"), "weight of the neighbour at offset (dx, dy, dz), each -1..1")
+      .def("set", [](BoxWeights &w, int dz, int dy, int dx, double v) {
+        STENCIL_REQUIRE(dz >= -1 && dz <= 1 && dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1, "BoxWeights offset");
+        w.w[dz + 1][dy + 1][dx + 1] = v;
+      }, py::arg("dz"), py::arg("dy"), py::arg("dx"), py::arg("value"));
+  m.def("stencil_box_supported",
+        [](DistributedDomain &dd, size_t di, int64_t q) { return stencil_box_supported(dd.domains().at(di), q); },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"));
+  m.def("stencil_box_apply",
+        [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &region, const BoxWeights &w, uintptr_t stream,
+           const StencilTune &tune) {
+          stencil_box_apply(dd.domains().at(di), q, region, w, reinterpret_cast<hipStream_t>(stream), tune);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("stream"),
+        py::arg("tune"), py::call_guard<py::gil_scoped_release>());
+  m.def("stencil_box_launch_info",
+        [](DistributedDomain &dd, size_t di, int64_t q, const Rect3 &region, const BoxWeights &w, const StencilTune &tune) {
+          // what stencil_box_apply would run (nothing is launched)
+          const BoxLaunchInfo r = stencil_box_launch_info(dd.domains().at(di), q, region, w, tune);
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["zchunk"] = r.zchunk;
+          o["zchunks"] = r.zchunks;
+          o["blocks"] = r.blocks;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("tune"));
   // ---------------- boundary fill ----------------
   auto fill_requests = [](const std::vector<int64_t> &qs, const std::vector<BoundaryConditions> &bcs, bool curr) {
     STENCIL_REQUIRE(qs.size() == bcs.size(), "boundary fill: " << qs.size() << " quantities, " << bcs.size() << " conditions");

@@ -1,5 +1,6 @@
 """Conjugate gradients for A u = f, where A is the operator ``ops.star_apply`` computes from symmetric star weights
-under physical boundary conditions (periodic, or Constant / Mirror / AntiMirror walls).
+(or ``ops.box_apply`` from symmetric 27-point box weights, e.g. the compact Laplacians of ``ops.laplacian_box``) under
+physical boundary conditions (periodic, or Constant / Mirror / AntiMirror walls).
 
 ``StarCG`` is a thin Python class over ``parallel.DistributedDomain`` with four quantities of one dtype, u, r, p and
 f. Every product A p is exchange + ``apply_boundary(p)`` + ``star_apply(p)`` (into next(p)), every vector update is
@@ -18,7 +19,7 @@ import math
 import torch
 
 from .. import _C
-from ..ops.kernels import field_axpby_supported, star_apply, star_supported
+from ..ops.kernels import box_apply, box_supported, field_axpby_supported, star_apply, star_supported
 from ..parallel.domain import DistributedDomain
 
 _AXES = ((0, (-1, 0, 0), (1, 0, 0)), (1, (0, -1, 0), (0, 1, 0)), (2, (0, 0, -1), (0, 0, 1)))
@@ -45,17 +46,49 @@ def _conditions(boundary, homogeneous: bool, all_open: bool = False):
     return bc
 
 
+def _check_box_symmetry(weights, boundary):
+    """A box gives a symmetric matrix when w(d) == w(-d) for all d and, for every non-periodic axis a, also
+    w(d) == w(d reflected in a): under Mirror / AntiMirror walls central symmetry alone does not (the ghost cell of a
+    wall row folds w(d) onto the reflected offset's column)."""
+    offs = (-1, 0, 1)
+    for dz in offs:
+        for dy in offs:
+            for dx in offs:
+                if weights.get(dz, dy, dx) != weights.get(-dz, -dy, -dx):
+                    raise ValueError(f"StarCG needs symmetric weights: offset (dz, dy, dx) = ({dz}, {dy}, {dx}): "
+                                     f"{weights.get(dz, dy, dx)} != {weights.get(-dz, -dy, -dx)} at the opposite offset")
+    if boundary is None:
+        return
+    for ax, lo, hi in _AXES:
+        if all(boundary.face(*d).kind == _C.FaceKind.Periodic for d in (lo, hi)):
+            continue
+        for dz in offs:
+            for dy in offs:
+                for dx in offs:
+                    r = [dz, dy, dx]
+                    r[2 - ax] = -r[2 - ax]
+                    if weights.get(dz, dy, dx) != weights.get(*r):
+                        raise ValueError(f"StarCG needs weights even along the walled axis {ax}: offset (dz, dy, dx) = "
+                                         f"({dz}, {dy}, {dx}): {weights.get(dz, dy, dx)} != {weights.get(*r)} at its "
+                                         f"reflection")
+
+
 class StarCG:
     def __init__(self, size, weights, fp64: bool = True, gpus=None, backend=None, methods=_C.MethodFlags.All,
                  group=None, boundary=None):
-        R = weights.radius
-        if R not in (1, 2, 3):
-            raise ValueError(f"star radius must be 1, 2 or 3, not {R}")
-        for ax in range(3):
-            for k in range(1, R + 1):
-                if weights.get(ax, 0, k) != weights.get(ax, 1, k):
-                    raise ValueError(f"StarCG needs symmetric weights: axis {ax}, offset {k}: "
-                                     f"{weights.get(ax, 0, k)} != {weights.get(ax, 1, k)}")
+        self._box = isinstance(weights, _C.BoxWeights)
+        if self._box:
+            R = 1
+            _check_box_symmetry(weights, boundary)
+        else:
+            R = weights.radius
+            if R not in (1, 2, 3):
+                raise ValueError(f"star radius must be 1, 2 or 3, not {R}")
+            for ax in range(3):
+                for k in range(1, R + 1):
+                    if weights.get(ax, 0, k) != weights.get(ax, 1, k):
+                        raise ValueError(f"StarCG needs symmetric weights: axis {ax}, offset {k}: "
+                                         f"{weights.get(ax, 0, k)} != {weights.get(ax, 1, k)}")
         if boundary is not None:
             for ax, lo, hi in _AXES:
                 for d in (lo, hi):
@@ -65,7 +98,8 @@ class StarCG:
         self.boundary = boundary
         self.dtype = torch.float64 if fp64 else torch.float32
         dd = DistributedDomain(*size, group=group)
-        dd.set_radius(_C.Radius.face_edge_corner(R, 0, 0))  # a star reads faces only
+        # a star reads faces only, a box edges and corners too
+        dd.set_radius(_C.Radius.face_edge_corner(1, 1, 1) if self._box else _C.Radius.face_edge_corner(R, 0, 0))
         dd.set_methods(methods)
         if gpus is not None:
             dd.set_gpus(list(gpus))
@@ -79,7 +113,8 @@ class StarCG:
                 dd.set_boundary_conditions(q, _conditions(boundary, False, all_open=True))
         dd.realize()
         for di in range(dd.num_domains()):
-            assert star_supported(dd, di, self.u, weights) and field_axpby_supported(dd, di, self.r, self.f, self.u)
+            ok = box_supported(dd, di, self.u) if self._box else star_supported(dd, di, self.u, weights)
+            assert ok and field_axpby_supported(dd, di, self.r, self.f, self.u)
         self._dd = dd
         self._size = tuple(int(v) for v in size)
         self.set_guess()
@@ -104,7 +139,10 @@ class StarCG:
         if self.boundary is not None:
             dd.apply_boundary(q)
         for di in range(dd.num_domains()):
-            star_apply(dd, di, q, self.weights)
+            if self._box:
+                box_apply(dd, di, q, self.weights)
+            else:
+                star_apply(dd, di, q, self.weights)
 
     @staticmethod
     def _finite(s, what):

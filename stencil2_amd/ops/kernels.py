@@ -258,3 +258,34 @@ def star_launch_info(dd, di: int, q: int, weights, region=None, tune=None) -> di
     if region is None:
         region = native.domain(di).get_compute_region()
     return _C.stencil_star_launch_info(native, di, q, region, weights, _tune(tune))
+
+
+def box_supported(dd, di: int, q: int) -> bool:
+    """True when `box_apply` can run on quantity q of local sub-domain di: an fp32 / fp64 quantity (or opaque 4- /
+    8-byte elements) and all 26 direction radii of the domain >= 1 (a 19-point box still needs the corners exchanged:
+    zero weights are multiplied like any other)."""
+    return _C.stencil_box_supported(getattr(dd, "native", dd), di, q)
+
+
+def box_apply(dd, di: int, q: int, weights, region=None, stream: int = 0, tune=None):
+    """next(region) = weighted 27-point box stencil of curr (`weights`: ops.box_weights / laplacian_box /
+    diffusion_box / smoothing_box) for quantity q of local sub-domain di; `region` (global coordinates) defaults to
+    the sub-domain's compute region and only its cells are written. The face, edge and corner halos of curr must be
+    valid to depth 1 (exchange() first). Every product and sum is its own rounding in the quantity's type, in the
+    order of `box_step_reference` (dz slowest, dx fastest, from (-1, -1, -1)), so the result is bitwise equal to it.
+    Of `tune`: zchunk, nontemporal, xcd_remap; alternate_z is ignored (every z chunk marches upwards, because the sum
+    takes dz = -1 first) and wrap != 0 is refused (csrc/src/kernels/stencil_box.hip)."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    _C.stencil_box_apply(native, di, q, region, weights, stream, _tune(tune))
+
+
+def box_launch_info(dd, di: int, q: int, weights, region=None, tune=None) -> dict:
+    """What `box_apply` would run for these arguments (nothing is launched; the same refusals raise): `path` ("fast":
+    the z-march kernel of the aligned vector layout, "generic": one thread per cell, "host", "none": empty region) and
+    the z-march launch `zchunk` (planes per block), `zchunks`, `blocks`."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return _C.stencil_box_launch_info(native, di, q, region, weights, _tune(tune))

@@ -134,6 +134,35 @@ def star_step_reference(u: torch.Tensor, weights, boundary=None) -> torch.Tensor
     return acc
 
 
+def box_step_reference(u: torch.Tensor, weights, boundary=None) -> torch.Tensor:
+    """One weighted 27-point box step (`weights`: _C.BoxWeights, see ops.box) on a global (z, y, x) grid: the oracle of
+    `box_apply`. acc = w(-1, -1, -1) * u(c + (-1, -1, -1)), then for every later (dz, dy, dx) in lexicographic order,
+    dz slowest and dx fastest: acc + w(dz, dy, dx) * u(c + (dx, dy, dz)). The weights are 0-dim tensors of u's dtype
+    (one conversion from double) and every product and every sum is a separate op, so each is rounded on its own in
+    that dtype. `boundary` (_C.BoundaryConditions): the neighbours beyond a non-periodic face, edge or corner come from
+    `pad_reference` (x, then y, then z); None is the periodic grid."""
+    def wt(v):
+        return torch.tensor(v, dtype=torch.float64).to(u.dtype).to(u.device)
+
+    if boundary is None:
+        def nb(dz, dy, dx):  # u(c + (dx, dy, dz))
+            return torch.roll(u, (-dz, -dy, -dx), (0, 1, 2))
+    else:
+        p = pad_reference(u, 1, boundary)
+        Z, Y, X = u.shape
+
+        def nb(dz, dy, dx):
+            return p[1 + dz:1 + dz + Z, 1 + dy:1 + dy + Y, 1 + dx:1 + dx + X]
+
+    acc = None
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                term = wt(weights.get(dz, dy, dx)) * nb(dz, dy, dx)
+                acc = term if acc is None else acc + term
+    return acc
+
+
 def axpby_reference(a, x: torch.Tensor, b=None, y=None) -> torch.Tensor:
     """a * x, or a * x + b * y: the oracle of `field_axpby`. a and b are 0-dim tensors of x's dtype (one conversion
     from double), and each product and the sum is a separate op, so each is rounded on its own in that dtype. A zero
@@ -262,4 +291,4 @@ def boundary_fill_reference(raw: torch.Tensor, origin, size, radius_lo, radius_h
 
 
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "axpby_reference", "pad_reference", "boundary_fill_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "box_step_reference", "axpby_reference", "pad_reference", "boundary_fill_reference", "math"]

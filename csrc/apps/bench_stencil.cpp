@@ -16,6 +16,7 @@
 #include "stencil/domain/local_domain.hpp"
 #include "stencil/domain/packer.hpp"
 #include "stencil/kernels/field_reduce.hpp"
+#include "stencil/kernels/grid_transfer.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/rt/argparse.hpp"
 #include "stencil/rt/stream.hpp"
@@ -67,7 +68,8 @@ int main(int argc, char **argv) {
       .option(&only, "--only", "run only 'lds', 'reg', 'copy', 'star' (weighted stars of radius 1-3 beside stencil7), 'box' (27-point boxes beside "
                              "stencil7 and the radius-1 star; 'boxzc': their z-chunk sweep) or 'reduce' (field "
                              "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange) or "
-                             "'axpby' (field algebra beside the field reductions)");
+                             "'axpby' (field algebra beside the field reductions) or 'transfer' (grid transfer n^3 <-> (n/2)^3 "
+                             "beside the one-operand reduction and the one-source axpby)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -669,6 +671,85 @@ int main(int argc, char **argv) {
     std::printf("axpby_condition,fused_update_median_us,%.2f,reduce1_plus_reduce2_median_us,%.2f,ratio,%.3f,bound,1.25,%s\n",
                 med[4], med[0] + med[1], med[4] / (med[0] + med[1]), med[4] <= bound ? "met" : "MISSED");
     std::printf("axpby_stores,plain_median_us,%.2f,nontemporal_median_us,%.2f\n", med[4], med[5]);
+  }
+  if (only == "transfer") {
+    // Grid transfer between n^3 and (n/2)^3 in fp32 and fp64 beside two unchanged yardsticks on the fine grid, all
+    // in one invocation and timed as under 'axpby' (blocking medians, interleaved per round, and back-to-back stream
+    // time). Restriction reads every fine cell once and writes 1/8 as many coarse cells (9/8 of the bytes the
+    // one-operand reduction reads); the correction u <- u + P e reads and writes every fine cell once and reads the
+    // coarse grid (17/16 of the bytes of the one-source axpby). Each must take at most 1.25 x its yardstick's median
+    // scaled by those bytes.
+    auto blocking_us = [&](auto &&fn, std::vector<double> &out) {
+      const auto t0 = std::chrono::steady_clock::now();
+      fn();
+      HIP_CHECK(hipStreamSynchronize(s));
+      out.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    };
+    auto median = [](std::vector<double> v) {
+      std::sort(v.begin(), v.end());
+      return v.empty() ? 0.0 : (v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]));
+    };
+    std::printf("kernel,dtype,path,blocks,median_us,fine_gcells,moved_TBps,stream_us\n");
+    auto run = [&](auto tag, const char *tname) {
+      using T = decltype(tag);
+      const double es = sizeof(T);
+      LocalDomain fd(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device), cd(Dim3(n / 2, n / 2, n / 2), Dim3(0, 0, 0), 0, Backend::Device);
+      fd.set_radius(Radius::face_edge_corner(1, 1, 1));
+      cd.set_radius(Radius::face_edge_corner(1, 1, 1));
+      for (const char *name : {"u", "r", "w"}) fd.add_data<T>(name);
+      for (const char *name : {"u", "f"}) cd.add_data<T>(name);
+      fd.realize();
+      cd.realize();
+      const Rect3 freg = fd.get_compute_region(), creg = cd.get_compute_region();
+      for (int q = 0; q < 3; ++q) fill_value(fd, q, 0.25 + q, true, s);
+      for (int q = 0; q < 2; ++q) fill_value(cd, q, 1e-3 * (q + 1), true, s);
+      s.sync();
+      ReduceScratch scratch;
+      const FieldRef u(0, true), r(1, true), w(2, true), cu(0, true), cf(1, true), none;
+      std::vector<std::function<void()>> fns = {
+          [&] { field_reduce_enqueue(fd, 1, true, -1, false, freg, scratch, s); },   // the yardstick of restriction
+          [&] { grid_restrict_enqueue(fd, r, cd, cf, creg, s); },                    // f_c <- R r
+          [&] { field_axpby_enqueue(fd, w, 0.5, r, 0.0, none, freg, s); },           // the yardstick of the correction
+          [&] { grid_prolong_enqueue(cd, cu, fd, u, u, freg, s); },                  // u <- u + P e
+          [&] { grid_prolong_enqueue(cd, cu, fd, w, none, freg, s); },               // w <- P e
+          [&] { grid_prolong_enqueue(cd, cu, fd, u, u, freg, s, 4); },               // u <- u + P e, shorter marches
+          [&] { grid_prolong_enqueue(cd, cu, fd, u, u, freg, s, 16); },              // ... and longer ones
+      };
+      const char *names[] = {"field_reduce_1", "grid_restrict", "field_axpby_1", "grid_prolong_add", "grid_prolong",
+                             "grid_prolong_add_zc4", "grid_prolong_add_zc16"};
+      const double bytes[] = {es, es * 9 / 8, 2 * es, es * 17 / 8, es * 9 / 8, es * 17 / 8, es * 17 / 8};
+      const ReduceLaunchInfo rli = field_reduce_launch_info(fd, 1, true, -1, false, freg);
+      const AxpbyLaunchInfo ali = field_axpby_launch_info(fd, w, 0.5, r, 0.0, none, freg);
+      const TransferLaunchInfo tli[] = {grid_restrict_launch_info(fd, r, cd, cf, creg),
+                                        grid_prolong_launch_info(cd, cu, fd, u, u, freg),
+                                        grid_prolong_launch_info(cd, cu, fd, w, none, freg),
+                                        grid_prolong_launch_info(cd, cu, fd, u, u, freg, 4),
+                                        grid_prolong_launch_info(cd, cu, fd, u, u, freg, 16)};
+      const int paths[] = {rli.path, tli[0].path, ali.path, tli[1].path, tli[2].path, tli[3].path, tli[4].path};
+      const long long blocks[] = {(long long)rli.blocks,    (long long)tli[0].blocks, (long long)ali.blocks, (long long)tli[1].blocks,
+                                  (long long)tli[2].blocks, (long long)tli[3].blocks, (long long)tli[4].blocks};
+      for (int i = 0; i < 3; ++i) // warm-up: first launches, scratch allocation
+        for (auto &f : fns) f();
+      s.sync();
+      std::vector<std::vector<double>> us(fns.size());
+      for (int rep = 0; rep < std::max(reps, 1); ++rep)
+        for (int i = 0; i < iters; ++i)
+          for (size_t k = 0; k < fns.size(); ++k) blocking_us(fns[k], us[k]);
+      std::vector<double> med(fns.size());
+      for (size_t k = 0; k < fns.size(); ++k) {
+        med[k] = median(us[k]);
+        const double st = timeit(fns[k]);
+        std::printf("%s,%s,%d,%lld,%.2f,%.1f,%.3f,%.2f\n", names[k], tname, paths[k], blocks[k], med[k],
+                    cells / med[k] / 1e3, cells * bytes[k] / med[k] / 1e6, st);
+      }
+      const double rb = 1.25 * 9 / 8 * med[0], pb = 1.25 * 17 / 16 * med[2];
+      std::printf("transfer_condition,%s,restrict_median_us,%.2f,reduce1_median_us,%.2f,ratio,%.3f,bound,%.4f,%s\n", tname,
+                  med[1], med[0], med[1] / med[0], 1.25 * 9 / 8, med[1] <= rb ? "met" : "MISSED");
+      std::printf("transfer_condition,%s,prolong_add_median_us,%.2f,axpby1_median_us,%.2f,ratio,%.3f,bound,%.4f,%s\n", tname,
+                  med[3], med[2], med[3] / med[2], 1.25 * 17 / 16, med[3] <= pb ? "met" : "MISSED");
+    };
+    run(float(), "fp32");
+    run(double(), "fp64");
   }
   for (int rep = 0; rep < reps; ++rep)
   if (only == "x2pp") {

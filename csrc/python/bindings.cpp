@@ -16,6 +16,7 @@
 #include "stencil/comm/rccl_comm.hpp"
 #include "stencil/domain/distributed_domain.hpp"
 #include "stencil/kernels/copy.hpp"
+#include "stencil/kernels/grid_transfer.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/models/stencil_model.hpp"
 #include "stencil/rt/build_info.hpp"
@@ -129,6 +130,13 @@ static Dim3 to_dim3(py::handle h) {
   auto t = h.cast<std::vector<int64_t>>();
   if (t.size() != 3) throw std::runtime_error("expected 3 coordinates");
   return Dim3(t[0], t[1], t[2]);
+}
+
+// local sub-domain di of a domain handed to the grid-transfer entry points (an unrealized domain has none)
+static LocalDomain &transfer_sub(DistributedDomain &dd, size_t di) {
+  STENCIL_REQUIRE(di < dd.domains().size(), "grid transfer: no local sub-domain " << di << " (" << dd.domains().size()
+                                                << " realized; an unrealized domain has none)");
+  return dd.domains()[di];
 }
 
 PYBIND11_MODULE(_C, m) {
@@ -744,6 +752,60 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dd"), py::arg("domain"), py::arg("qdst"), py::arg("curr_dst"), py::arg("a"), py::arg("qx"),
         py::arg("curr_x"), py::arg("b"), py::arg("qy"), py::arg("curr_y"), py::arg("region"), py::arg("stats") = false,
         py::arg("max_blocks") = 0, py::arg("nontemporal") = false);
+
+  // ---------------- grid transfer ----------------
+  m.def("grid_transfer_supported",
+        [](DistributedDomain &fine, DistributedDomain &coarse, size_t di, int64_t qf, int64_t qc) {
+          return grid_transfer_supported(transfer_sub(fine, di), qf, transfer_sub(coarse, di), qc);
+        },
+        py::arg("fine"), py::arg("coarse"), py::arg("domain"), py::arg("qf"), py::arg("qc"));
+  m.def("grid_restrict",
+        [](DistributedDomain &fine, DistributedDomain &coarse, size_t di, int64_t src, bool currSrc, int64_t dst,
+           bool currDst, const Rect3 &region, uintptr_t stream) {
+          grid_restrict_enqueue(transfer_sub(fine, di), FieldRef(src, currSrc), transfer_sub(coarse, di),
+                                FieldRef(dst, currDst), region, reinterpret_cast<hipStream_t>(stream));
+        },
+        py::arg("fine"), py::arg("coarse"), py::arg("domain"), py::arg("src"), py::arg("curr_src"), py::arg("dst"),
+        py::arg("curr_dst"), py::arg("region"), py::arg("stream") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def("grid_prolong",
+        [](DistributedDomain &coarse, DistributedDomain &fine, size_t di, int64_t src, bool currSrc, int64_t dst,
+           bool currDst, int64_t add, bool currAdd, const Rect3 &region, uintptr_t stream, int zchunk) {
+          grid_prolong_enqueue(transfer_sub(coarse, di), FieldRef(src, currSrc), transfer_sub(fine, di),
+                               FieldRef(dst, currDst), FieldRef(add, currAdd), region,
+                               reinterpret_cast<hipStream_t>(stream), zchunk);
+        },
+        py::arg("coarse"), py::arg("fine"), py::arg("domain"), py::arg("src"), py::arg("curr_src"), py::arg("dst"),
+        py::arg("curr_dst"), py::arg("add"), py::arg("curr_add"), py::arg("region"), py::arg("stream") = 0,
+        py::arg("zchunk") = 0, py::call_guard<py::gil_scoped_release>());
+  {
+    // what grid_restrict / grid_prolong would run (nothing is launched)
+    auto as_dict = [](const TransferLaunchInfo &r) {
+      static const char *names[] = {"none", "host", "generic", "fast"};
+      py::dict o;
+      o["path"] = names[r.path + 1];
+      o["blocks"] = r.blocks;
+      o["items"] = r.items;
+      o["zchunk"] = r.zchunk;
+      return o;
+    };
+    m.def("grid_restrict_launch_info",
+          [as_dict](DistributedDomain &fine, DistributedDomain &coarse, size_t di, int64_t src, bool currSrc, int64_t dst,
+                    bool currDst, const Rect3 &region) {
+            return as_dict(grid_restrict_launch_info(transfer_sub(fine, di), FieldRef(src, currSrc),
+                                                     transfer_sub(coarse, di), FieldRef(dst, currDst), region));
+          },
+          py::arg("fine"), py::arg("coarse"), py::arg("domain"), py::arg("src"), py::arg("curr_src"), py::arg("dst"),
+          py::arg("curr_dst"), py::arg("region"));
+    m.def("grid_prolong_launch_info",
+          [as_dict](DistributedDomain &coarse, DistributedDomain &fine, size_t di, int64_t src, bool currSrc, int64_t dst,
+                    bool currDst, int64_t add, bool currAdd, const Rect3 &region, int zchunk) {
+            return as_dict(grid_prolong_launch_info(transfer_sub(coarse, di), FieldRef(src, currSrc),
+                                                    transfer_sub(fine, di), FieldRef(dst, currDst),
+                                                    FieldRef(add, currAdd), region, zchunk));
+          },
+          py::arg("coarse"), py::arg("fine"), py::arg("domain"), py::arg("src"), py::arg("curr_src"), py::arg("dst"),
+          py::arg("curr_dst"), py::arg("add"), py::arg("curr_add"), py::arg("region"), py::arg("zchunk") = 0);
+  }
 
   py::class_<DistributedDomain, std::shared_ptr<DistributedDomain>>(m, "DistributedDomain")
       .def("axpby",

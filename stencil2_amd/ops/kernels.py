@@ -289,3 +289,76 @@ def box_launch_info(dd, di: int, q: int, weights, region=None, tune=None) -> dic
     if region is None:
         region = native.domain(di).get_compute_region()
     return _C.stencil_box_launch_info(native, di, q, region, weights, _tune(tune))
+
+
+def _native(dd):
+    return getattr(dd, "native", dd)
+
+
+def _sub_region(native, di):
+    """the compute region of local sub-domain di, the default region of a grid transfer"""
+    n = native.num_domains()
+    if not 0 <= di < n:
+        raise IndexError(f"grid transfer: no local sub-domain {di} ({n} realized; an unrealized domain has none)")
+    return native.domain(di).get_compute_region()
+
+
+def grid_transfer_supported(fine_dd, coarse_dd, di: int, qf: int, qc: int) -> bool:
+    """True when `restrict_apply` / `prolong_apply` take quantity qf of local sub-domain di of `fine_dd` and qc of the
+    same sub-domain of `coarse_dd`: fp32 / fp64 quantities (or opaque 4- / 8-byte elements) of one element size, both
+    domains realized, the coarse sub-domain the factor-2 image of the fine one (even origin and size, halved) on the
+    same device and backend. Prolongation also needs every coarse direction radius >= 1."""
+    return _C.grid_transfer_supported(_native(fine_dd), _native(coarse_dd), di, int(qf), int(qc))
+
+
+def restrict_apply(fine_dd, coarse_dd, di: int, src: int, dst: int, src_curr: bool = True, dst_curr: bool = True,
+                   region=None, stream: int = 0):
+    """coarse dst(region) = R fine src between local sub-domain di of the two domains: cell-centred full weighting, the
+    mean of the 8 fine cells under a coarse cell summed along x, then y, then z, every sum rounded on its own in the
+    quantities' type, so the result is bitwise equal to `restrict_reference`. `region` (global coordinates of the
+    coarse grid) defaults to the coarse sub-domain's compute region; only its cells are written and no halo is read.
+    Asynchronous on `stream` (csrc/src/kernels/grid_transfer.hip)."""
+    fine, coarse = _native(fine_dd), _native(coarse_dd)
+    if region is None:
+        region = _sub_region(coarse, di)
+    _C.grid_restrict(fine, coarse, di, int(src), bool(src_curr), int(dst), bool(dst_curr), region, stream)
+
+
+def restrict_launch_info(fine_dd, coarse_dd, di: int, src: int, dst: int, src_curr: bool = True, dst_curr: bool = True,
+                         region=None) -> dict:
+    """What `restrict_apply` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the chunk kernel of the aligned vector layout, "generic": one thread per coarse cell, "host", "none":
+    empty region), `blocks` of the launch and `items`, the coarse (row, plane) pairs of the region."""
+    fine, coarse = _native(fine_dd), _native(coarse_dd)
+    if region is None:
+        region = _sub_region(coarse, di)
+    return _C.grid_restrict_launch_info(fine, coarse, di, int(src), bool(src_curr), int(dst), bool(dst_curr), region)
+
+
+def prolong_apply(coarse_dd, fine_dd, di: int, src: int, dst: int, add=None, src_curr: bool = True,
+                  dst_curr: bool = True, add_curr: bool = True, region=None, stream: int = 0, zchunk: int = 0):
+    """fine dst(region) = P coarse src, or with `add` (a quantity of the fine domain, possibly dst itself: the
+    correction u <- u + P e) add + P coarse src, between local sub-domain di of the two domains. P is trilinear
+    (weights 3/4 and 1/4 per axis), evaluated along x, then y, then z with every product and sum rounded on its own,
+    so the result is bitwise equal to `prolong_reference`. It reads one cell into the coarse halos in all 26
+    directions: exchange the coarse domain and `apply_boundary` first. `region` (global coordinates of the fine grid)
+    defaults to the fine sub-domain's compute region; only its cells are written. `zchunk`: the coarse planes a wave
+    of the chunk kernel marches (0: chosen by the launch). Asynchronous on `stream` (csrc/src/kernels/grid_transfer.hip)."""
+    coarse, fine = _native(coarse_dd), _native(fine_dd)
+    if region is None:
+        region = _sub_region(fine, di)
+    _C.grid_prolong(coarse, fine, di, int(src), bool(src_curr), int(dst), bool(dst_curr),
+                    -1 if add is None else int(add), bool(add_curr), region, stream, int(zchunk))
+
+
+def prolong_launch_info(coarse_dd, fine_dd, di: int, src: int, dst: int, add=None, src_curr: bool = True,
+                        dst_curr: bool = True, add_curr: bool = True, region=None, zchunk: int = 0) -> dict:
+    """What `prolong_apply` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the z-march chunk kernel of the aligned vector layout, "generic": one thread per fine cell, "host",
+    "none": empty region), `blocks`, `items` ((64 fine chunks, coarse row, z chunk) triples, one wave each) and `zchunk`
+    (coarse planes per item)."""
+    coarse, fine = _native(coarse_dd), _native(fine_dd)
+    if region is None:
+        region = _sub_region(fine, di)
+    return _C.grid_prolong_launch_info(coarse, fine, di, int(src), bool(src_curr), int(dst), bool(dst_curr),
+                                       -1 if add is None else int(add), bool(add_curr), region, int(zchunk))

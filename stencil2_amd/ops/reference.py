@@ -290,5 +290,77 @@ def boundary_fill_reference(raw: torch.Tensor, origin, size, radius_lo, radius_h
     return (out, written) if return_mask else out
 
 
+# ---- grid transfer and the multigrid cycle (csrc/include/stencil/kernels/grid_transfer.hpp) ----
+def restrict_reference(r: torch.Tensor) -> torch.Tensor:
+    """Cell-centred full weighting of a global (z, y, x) grid with even extents: the oracle of `restrict_apply`. The 8
+    fine cells under a coarse cell are summed along x, then y, then z, each sum a separate op, then scaled by 0.125."""
+    sx = r[:, :, 0::2] + r[:, :, 1::2]
+    sy = sx[:, 0::2] + sx[:, 1::2]
+    return 0.125 * (sy[0::2] + sy[1::2])
+
+
+def _interp_reference(p: torch.Tensor, ax: int) -> torch.Tensor:
+    """p padded by one cell along ax: fine cell 2 I is 0.75 p(I) + 0.25 p(I - 1), fine cell 2 I + 1 is
+    0.75 p(I) + 0.25 p(I + 1)"""
+    n = p.shape[ax] - 2
+    c, lo, hi = p.narrow(ax, 1, n), p.narrow(ax, 0, n), p.narrow(ax, 2, n)
+    return torch.stack([0.75 * c + 0.25 * lo, 0.75 * c + 0.25 * hi], ax + 1).flatten(ax, ax + 1)
+
+
+def prolong_reference(c: torch.Tensor, boundary=None, add=None) -> torch.Tensor:
+    """Trilinear cell-centred prolongation of a global (z, y, x) coarse grid to twice the extents: the oracle of
+    `prolong_apply`. The grid is padded by one cell (`pad_reference(c, 1, boundary)`; None: the periodic wrap) and
+    interpolated along x, then y, then z with weights 0.75 (near) and 0.25 (far), every product and sum a separate op;
+    with `add` the result is add + P c (one more sum, add on the left)."""
+    if boundary is None:
+        p = c
+        for dim in (2, 1, 0):
+            n = p.shape[dim]
+            p = torch.cat([p.narrow(dim, n - 1, 1), p, p.narrow(dim, 0, 1)], dim=dim)
+    else:
+        p = pad_reference(c, 1, boundary)
+    v = _interp_reference(_interp_reference(_interp_reference(p, 2), 1), 0)
+    return v if add is None else add + v
+
+
+def mg_cycle_reference(u: torch.Tensor, f: torch.Tensor, weights_per_level, bc, nu=(2, 2), omega: float = 6.0 / 7.0,
+                       coarse_sweeps: int = 32) -> torch.Tensor:
+    """One V-cycle of `models.StarMG` on gathered global (z, y, x) grids, with the same scalars in the same order: the
+    oracle of `StarMG.cycle`. `weights_per_level[l]` is the operator of level l (StarWeights or BoxWeights), `bc` the
+    conditions of u at level 0 (None: periodic); coarser levels take its homogeneous twin. A smoothing sweep is
+    u <- 1.0 * (S u) + c * f with c = omega / centre(A_l) and S = `ops.smoother_weights(A_l, c)`; the residual is
+    1.0 * f + (-1.0) * (A_l u); the coarse problem starts from 0 and the coarsest level runs `coarse_sweeps` sweeps.
+    Returns u after the cycle. The smoother's weights and the homogeneous conditions are built by the solver's own
+    helpers (`ops.smoother_weights`, `models.star_cg._conditions`): the oracle checks the cycle's composition and
+    arithmetic, not those two constructions, which the convergence limits of the tests guard."""
+    from .multigrid import smoother_weights, weights_center
+    from .. import _C
+    from ..models.star_cg import _conditions
+
+    hom = None if bc is None else _conditions(bc, True)
+    last = len(weights_per_level) - 1
+
+    def cycle(level, u, f, cond):
+        A = weights_per_level[level]
+        step = box_step_reference if isinstance(A, _C.BoxWeights) else star_step_reference
+        c = omega / weights_center(A)
+        S = smoother_weights(A, c)
+
+        def smooth(u, sweeps):
+            for _ in range(sweeps):
+                u = axpby_reference(1.0, step(u, S, boundary=cond), c, f)
+            return u
+
+        if level == last:
+            return smooth(u, coarse_sweeps)
+        u = smooth(u, nu[0])
+        r = axpby_reference(1.0, f, -1.0, step(u, A, boundary=cond))
+        e = cycle(level + 1, torch.zeros_like(restrict_reference(r)), restrict_reference(r), hom)
+        u = prolong_reference(e, boundary=hom, add=u)
+        return smooth(u, nu[1])
+
+    return cycle(0, u, f, bc)
+
+
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "box_step_reference", "axpby_reference", "pad_reference", "boundary_fill_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "box_step_reference", "axpby_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]

@@ -69,7 +69,8 @@ int main(int argc, char **argv) {
                              "stencil7 and the radius-1 star; 'boxzc': their z-chunk sweep) or 'reduce' (field "
                              "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange) or "
                              "'axpby' (field algebra beside the field reductions) or 'transfer' (grid transfer n^3 <-> (n/2)^3 "
-                             "beside the one-operand reduction and the one-source axpby)");
+                             "beside the one-operand reduction and the one-source axpby) or 'varcoef' (the "
+                             "variable-coefficient stencil beside the radius-1 star at n^3 and (n/2)^3, fp32 and fp64)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -457,6 +458,52 @@ int main(int argc, char **argv) {
         }
       }
     }
+  }
+  if (only == "varcoef") {
+    // the variable-coefficient stencil (u and kappa read, next(u) written: three fields) beside the radius-1 star (two
+    // fields) on the same domain, interleaved per repetition, at n^3 and (n / 2)^3, fp32 and fp64. The variant column
+    // holds the element type and the cube edge; eff_TBps counts three fields for varcoef, two for the star.
+    StarWeights sw;
+    sw.radius = 1;
+    sw.center = 0.25;
+    for (int ax = 0; ax < 3; ++ax)
+      for (int sd = 0; sd < 2; ++sd) sw.w[ax][sd][0] = 0.125;
+    VarCoefWeights vw; // an explicit diffusion step (values do not matter)
+    vw.shift = 1.0;
+    vw.h[0] = 0.02;
+    vw.h[1] = 0.03;
+    vw.h[2] = 0.025;
+    for (int64_t m : {n, n / 2})
+      for (int f64 = 0; f64 < 2; ++f64) {
+        const double es = f64 ? 8 : 4, mcells = double(m) * m * m;
+        LocalDomain lv(Dim3(m, m, m), Dim3(0, 0, 0), 0, Backend::Device);
+        lv.set_radius(Radius::face_edge_corner(1, 0, 0));
+        if (f64) {
+          lv.add_data<double>("u");
+          lv.add_data<double>("kappa");
+        } else {
+          lv.add_data<float>("u");
+          lv.add_data<float>("kappa");
+        }
+        lv.realize();
+        fill_value(lv, 0, 0.5, true, s);
+        fill_value(lv, 1, 1.5, true, s);
+        s.sync();
+        const Rect3 regv = lv.get_compute_region();
+        char tag[32];
+        std::snprintf(tag, sizeof tag, "%s_%lld", f64 ? "fp64" : "fp32", (long long)m);
+        for (int rep = 0; rep < reps; ++rep) {
+          StencilTune t;
+          const StarLaunchInfo si = stencil_star_launch_info(lv, 0, regv, sw, t);
+          const double uss = timeit([&] { stencil_star_apply(lv, 0, regv, sw, s, t); });
+          std::printf("stencil_star,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", tag, si.zchunk, uss, mcells / uss / 1e3,
+                      mcells * 2 * es / uss / 1e6, si.path);
+          const VarCoefLaunchInfo vi = stencil_varcoef_launch_info(lv, 0, 1, regv, vw, t);
+          const double usv = timeit([&] { stencil_varcoef_apply(lv, 0, 1, regv, vw, s, t); });
+          std::printf("stencil_varcoef,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", tag, vi.zchunk, usv, mcells / usv / 1e3,
+                      mcells * 3 * es / usv / 1e6, vi.path);
+        }
+      }
   }
   if (only == "bc") {
     // Boundary fill beside the periodic exchange of the same domain (fp32, face radius 3, one GPU): (a) the exchange

@@ -427,6 +427,46 @@ struct BoxLaunchInfo {
 BoxLaunchInfo stencil_box_launch_info(const LocalDomain &dom, int64_t qi, const Rect3 &region, const BoxWeights &w,
                                       const StencilTune &tune = StencilTune());
 
+// Variable-coefficient diffusion stencil (stencil_varcoef.hip): for a quantity u and a coefficient quantity k of the
+// same element type T (fp32 / fp64) in one LocalDomain
+//   acc = shift * u(c); for axis a in x, y, z:
+//     km = k(c) + k(c - e_a); dm = u(c - e_a) - u(c); fm = km * dm; tm = h[a] * fm; acc = acc + tm
+//     kp = k(c) + k(c + e_a); dp = u(c + e_a) - u(c); fp = kp * dp; tp = h[a] * fp; acc = acc + tp
+//   next(u)(c) = acc
+// with shift and h converted to T once on the host and every sum, difference and product its own IEEE rounding in T in
+// exactly this order (no FMA contraction; zero factors are multiplied like any other, so NaN / Inf propagate). The
+// face coefficient is the arithmetic mean with the 1/2 inside h: div(k grad u) at spacing hx takes h[0] = 1 / (2 hx^2).
+// k(c) + k(n) is commutative, so the coupling of two cells is bitwise the same from both sides: the operator is
+// symmetric by construction. Bitwise equal to stencil2_amd.ops.varcoef_step_reference.
+struct VarCoefWeights {
+  double shift = 0;
+  double h[3] = {0, 0, 0}; // one scale per axis x, y, z
+};
+// fp32 / fp64 quantities (or opaque 4- / 8-byte elements) of one element size and row pitch in a realized domain
+// whose six face radii are >= 1
+bool stencil_varcoef_supported(const LocalDomain &dom, int64_t qu, int64_t qk);
+// next(u)(region) = the operator above on curr(u) and curr(k); only next(u) is written, and only cells of `region`
+// (global coordinates, inside the compute region; empty: no-op), so qk == qu is allowed. Face neighbours of u and of k
+// come from the halos of their curr buffers (exchange() both first; Radius::face_edge_corner(1, 0, 0) suffices). Device
+// sub-domains in the aligned vector layout (as stencil_star_apply's) run a 2.5D z-march carrying both fields: one 16-B
+// x chunk of 2 rows per lane, per field the centre plane, the plane ahead and the entering plane in registers (the
+// face term towards the plane behind is computed a step early from the same operands and carried), the block's 16 rows
+// plus one halo row each side of both fields shared through LDS (73 728 B per block), x neighbours from adjacent lanes,
+// each source cell of both fields read from HBM about once per sweep; any other layout runs one thread per cell,
+// Backend::Host a plain loop. Of `tune`: zchunk (0 = one round of resident blocks, at most two per CU, chunks of >= 16 planes), nontemporal,
+// xcdRemap, alternateZ; tune.wrap != 0 is refused.
+void stencil_varcoef_apply(const LocalDomain &dom, int64_t qu, int64_t qk, const Rect3 &region, const VarCoefWeights &w,
+                           hipStream_t stream, const StencilTune &tune = StencilTune());
+// What stencil_varcoef_apply would run for these arguments (nothing is launched; the same refusals raise)
+struct VarCoefLaunchInfo {
+  int path = 0;       // -1 nothing (empty region), 0 host loop, 1 one thread per cell, 2 the z-march kernel
+  int zchunk = 0;     // z-march: planes per block
+  int zchunks = 0;    // z-march: chunks along z
+  int64_t blocks = 0; // z-march: blocks of the launch
+};
+VarCoefLaunchInfo stencil_varcoef_launch_info(const LocalDomain &dom, int64_t qu, int64_t qk, const Rect3 &region,
+                                              const VarCoefWeights &w, const StencilTune &tune = StencilTune());
+
 // Jacobi init: curr = 0.5 on `region` (reference bin/jacobi3d.cu:18-29)
 void jacobi_init(const LocalDomain &dom, int64_t qi, const Rect3 &region, hipStream_t stream);
 // Astaroth init: interior = sin(2*pi/period*(origin+x+y+z)) (x,y,z raw indices), halo = -10 (astaroth_sim.cu:14-61)

@@ -1118,8 +1118,51 @@ PYBIND11_MODULE(_C, m) {
           return o;
         },
         py::arg("dd"), py::arg("domain"), py::arg("qi"), py::arg("region"), py::arg("weights"), py::arg("tune"));
+  py::class_<VarCoefWeights>(m, "VarCoefWeights")
+      .def(py::init<>())
+      .def_readwrite("shift", &VarCoefWeights::shift)
+      .def_property(
+          "h", [](const VarCoefWeights &w) { return std::vector<double>{w.h[0], w.h[1], w.h[2]}; },
+          [](VarCoefWeights &w, const std::vector<double> &h) {
+            STENCIL_REQUIRE(h.size() == 3, "VarCoefWeights.h takes three values (x, y, z)");
+            for (int a = 0; a < 3; ++a) w.h[a] = h[size_t(a)];
+          },
+          "the scales of the x, y and z faces")
+      .def("__repr__", [](const VarCoefWeights &w) {
+        std::ostringstream os;
+        os.precision(17);
+        os << "VarCoefWeights(shift=" << w.shift << ", h=(" << w.h[0] << ", " << w.h[1] << ", " << w.h[2] << "))";
+        return os.str();
+      });
+  m.def("stencil_varcoef_supported",
+        [](DistributedDomain &dd, size_t di, int64_t qu, int64_t qk) {
+          return stencil_varcoef_supported(dd.domains().at(di), qu, qk);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"));
+  m.def("stencil_varcoef_apply",
+        [](DistributedDomain &dd, size_t di, int64_t qu, int64_t qk, const Rect3 &region, const VarCoefWeights &w,
+           uintptr_t stream, const StencilTune &tune) {
+          stencil_varcoef_apply(dd.domains().at(di), qu, qk, region, w, reinterpret_cast<hipStream_t>(stream), tune);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"), py::arg("region"), py::arg("weights"),
+        py::arg("stream"), py::arg("tune"), py::call_guard<py::gil_scoped_release>());
+  m.def("stencil_varcoef_launch_info",
+        [](DistributedDomain &dd, size_t di, int64_t qu, int64_t qk, const Rect3 &region, const VarCoefWeights &w,
+           const StencilTune &tune) {
+          // what stencil_varcoef_apply would run (nothing is launched)
+          const VarCoefLaunchInfo r = stencil_varcoef_launch_info(dd.domains().at(di), qu, qk, region, w, tune);
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["zchunk"] = r.zchunk;
+          o["zchunks"] = r.zchunks;
+          o["blocks"] = r.blocks;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"), py::arg("region"), py::arg("weights"),
+        py::arg("tune"));
   // ---------------- boundary fill ----------------
-  auto fill_requests = [](const std::vector<int64_t> &qs, const std::vector<BoundaryConditions> &bcs, bool curr) {
+  auto fill_requests =[](const std::vector<int64_t> &qs, const std::vector<BoundaryConditions> &bcs, bool curr) {
     STENCIL_REQUIRE(qs.size() == bcs.size(), "boundary fill: " << qs.size() << " quantities, " << bcs.size() << " conditions");
     std::vector<FillRequest> reqs(qs.size());
     for (size_t i = 0; i < qs.size(); ++i) {

@@ -9,6 +9,11 @@ f. Every product A p is exchange + ``apply_boundary(p)`` + ``star_apply(p)`` (in
 AntiMirror value 0); r and f take Open faces. An inhomogeneous wall therefore enters once, through
 r0 = f - A_bc(u0), and every later product is with the linear operator.
 
+With ``VarCoefWeights`` (``ops.operator_varcoef``) and ``kappa=fn`` A is the variable-coefficient operator of
+``ops.varcoef_apply``: a fifth quantity, kappa, is added after u, r, p and f, filled from ``fn`` and given its halos and
+ghost cells once at construction (``kappa_boundary``; None = Mirror on every non-periodic face of ``boundary``). That
+operator is symmetric by construction, so no symmetry check applies.
+
 Singular operators (a periodic or all-Mirror Laplacian with no centre shift) are the caller's responsibility: f must
 sum to zero, and the solver does no projection.
 """
@@ -19,8 +24,10 @@ import math
 import torch
 
 from .. import _C
-from ..ops.kernels import box_apply, box_supported, field_axpby_supported, star_apply, star_supported
+from ..ops.kernels import (box_apply, box_supported, field_axpby_supported, star_apply, star_supported, varcoef_apply,
+                           varcoef_supported)
 from ..parallel.domain import DistributedDomain
+from .varcoef_model import kappa_conditions, refuse_open
 
 _AXES = ((0, (-1, 0, 0), (1, 0, 0)), (1, (0, -1, 0), (0, 1, 0)), (2, (0, 0, -1), (0, 0, 1)))
 
@@ -75,9 +82,20 @@ def _check_box_symmetry(weights, boundary):
 
 class StarCG:
     def __init__(self, size, weights, fp64: bool = True, gpus=None, backend=None, methods=_C.MethodFlags.All,
-                 group=None, boundary=None):
+                 group=None, boundary=None, kappa=None, kappa_boundary=None):
         self._box = isinstance(weights, _C.BoxWeights)
-        if self._box:
+        self._varcoef = isinstance(weights, _C.VarCoefWeights)
+        if self._varcoef and kappa is None:
+            raise ValueError("StarCG on VarCoefWeights needs the coefficient: kappa=fn(gz, gy, gx)")
+        if not self._varcoef and (kappa is not None or kappa_boundary is not None):
+            raise ValueError(f"kappa= / kappa_boundary= belong to VarCoefWeights, not {type(weights).__name__}")
+        if self._varcoef:
+            # symmetric by construction: kappa(c) + kappa(n) is the same sum from both sides
+            R = 1
+            if boundary is None and kappa_boundary is not None:
+                raise ValueError("kappa_boundary needs boundary: the periodic faces of u and kappa are the grid's")
+            refuse_open(kappa_boundary, "StarCG (kappa)")
+        elif self._box:
             R = 1
             _check_box_symmetry(weights, boundary)
         else:
@@ -106,17 +124,31 @@ class StarCG:
         if backend is not None:
             dd.set_backend(backend)
         self.u, self.r, self.p, self.f = (dd.add_data(n, self.dtype) for n in ("u", "r", "p", "f"))
+        # the coefficient comes after u, r, p, f, so their indices are the same for every kind of weights
+        self.kappa = dd.add_data("kappa", self.dtype) if self._varcoef else None
         if boundary is not None:
             dd.set_boundary_conditions(boundary)
             dd.set_boundary_conditions(self.p, _conditions(boundary, True))
             for q in (self.r, self.f):
                 dd.set_boundary_conditions(q, _conditions(boundary, False, all_open=True))
+            if self._varcoef:
+                dd.set_boundary_conditions(self.kappa, kappa_conditions(boundary, kappa_boundary))
         dd.realize()
         for di in range(dd.num_domains()):
-            ok = box_supported(dd, di, self.u) if self._box else star_supported(dd, di, self.u, weights)
+            if self._varcoef:
+                ok = varcoef_supported(dd, di, self.u, self.kappa) and varcoef_supported(dd, di, self.p, self.kappa)
+            else:
+                ok = box_supported(dd, di, self.u) if self._box else star_supported(dd, di, self.u, weights)
             assert ok and field_axpby_supported(dd, di, self.r, self.f, self.u)
         self._dd = dd
         self._size = tuple(int(v) for v in size)
+        if self._varcoef:
+            # CG never swaps, so curr(kappa) is the coefficient for good: its halos and ghost cells are set once here
+            # (the exchange inside every product re-sends the same values)
+            dd.fill_from_global(self.kappa, kappa)
+            dd.exchange()
+            if boundary is not None:
+                dd.apply_boundary(self.kappa)
         self.set_guess()
 
     def _zero(self, gz, gy, gx):
@@ -139,7 +171,9 @@ class StarCG:
         if self.boundary is not None:
             dd.apply_boundary(q)
         for di in range(dd.num_domains()):
-            if self._box:
+            if self._varcoef:
+                varcoef_apply(dd, di, q, self.kappa, self.weights)
+            elif self._box:
                 box_apply(dd, di, q, self.weights)
             else:
                 star_apply(dd, di, q, self.weights)

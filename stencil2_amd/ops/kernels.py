@@ -291,6 +291,37 @@ def box_launch_info(dd, di: int, q: int, weights, region=None, tune=None) -> dic
     return _C.stencil_box_launch_info(native, di, q, region, weights, _tune(tune))
 
 
+def varcoef_supported(dd, di: int, q: int, kappa: int) -> bool:
+    """True when `varcoef_apply` can run on quantity q with the coefficient quantity `kappa` of local sub-domain di:
+    fp32 / fp64 quantities (or opaque 4- / 8-byte elements) of one element size and row pitch, and all six face radii
+    of the domain >= 1."""
+    return _C.stencil_varcoef_supported(getattr(dd, "native", dd), di, int(q), int(kappa))
+
+
+def varcoef_apply(dd, di: int, q: int, kappa: int, w, region=None, stream: int = 0, tune=None):
+    """next(q)(region) = w.shift * u + sum over the six faces of w.h[axis] * (kappa(c) + kappa(n)) * (u(n) - u(c)) with
+    u = curr(q) and kappa = curr(kappa) of local sub-domain di (`w`: ops.varcoef_weights / diffusion_varcoef /
+    operator_varcoef); `region` (global coordinates) defaults to the sub-domain's compute region and only its cells of
+    next(q) are written, so kappa == q is allowed. The face halos of both curr buffers must be valid to depth 1
+    (exchange() first). Every sum, difference and product is its own rounding in the quantities' type, in the order of
+    `varcoef_step_reference`, so the result is bitwise equal to it. Of `tune`: zchunk, nontemporal, xcd_remap,
+    alternate_z; wrap != 0 is refused (csrc/src/kernels/stencil_varcoef.hip)."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    _C.stencil_varcoef_apply(native, di, int(q), int(kappa), region, w, stream, _tune(tune))
+
+
+def varcoef_launch_info(dd, di: int, q: int, kappa: int, w, region=None, tune=None) -> dict:
+    """What `varcoef_apply` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the z-march kernel of the aligned vector layout, "generic": one thread per cell, "host", "none": empty
+    region) and the z-march launch `zchunk` (planes per block), `zchunks`, `blocks`."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return _C.stencil_varcoef_launch_info(native, di, int(q), int(kappa), region, w, _tune(tune))
+
+
 def _native(dd):
     return getattr(dd, "native", dd)
 

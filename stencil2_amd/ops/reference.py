@@ -163,6 +163,41 @@ def box_step_reference(u: torch.Tensor, weights, boundary=None) -> torch.Tensor:
     return acc
 
 
+def varcoef_step_reference(u: torch.Tensor, kappa: torch.Tensor, w, boundary=None, kappa_boundary=None) -> torch.Tensor:
+    """One variable-coefficient step (`w`: _C.VarCoefWeights, see ops.varcoef) on global (z, y, x) grids: the oracle of
+    `varcoef_apply`. acc = shift * u, then per axis x, y, z first the low face, then the high face:
+    ks = kappa + kappa(n); d = u(n) - u; f = ks * d; t = h[axis] * f; acc = acc + t. shift and h are 0-dim tensors of
+    u's dtype (one conversion from double) and every sum, difference and product is a separate op, so each is rounded
+    on its own in that dtype. `boundary` / `kappa_boundary` (_C.BoundaryConditions): the neighbours of u / kappa beyond
+    a non-periodic face come from `pad_reference`; None is the periodic grid."""
+    def wt(v):
+        return torch.tensor(v, dtype=torch.float64).to(u.dtype).to(u.device)
+
+    def neighbours(g, bc):
+        if bc is None:
+            return lambda k, dim: torch.roll(g, k, dim)  # g(c - k e)
+        p = pad_reference(g, 1, bc)
+        Z, Y, X = g.shape
+
+        def nb(k, dim):
+            lo = [1, 1, 1]
+            lo[dim] -= k
+            return p[lo[0]:lo[0] + Z, lo[1]:lo[1] + Y, lo[2]:lo[2] + X]
+        return nb
+
+    un, kn = neighbours(u, boundary), neighbours(kappa, kappa_boundary)
+    h = list(w.h)
+    acc = wt(w.shift) * u
+    for ax, dim in enumerate((2, 1, 0)):
+        for k in (1, -1):  # c - e, then c + e
+            ks = kappa + kn(k, dim)
+            d = un(k, dim) - u
+            f = ks * d
+            t = wt(h[ax]) * f
+            acc = acc + t
+    return acc
+
+
 def axpby_reference(a, x: torch.Tensor, b=None, y=None) -> torch.Tensor:
     """a * x, or a * x + b * y: the oracle of `field_axpby`. a and b are 0-dim tensors of x's dtype (one conversion
     from double), and each product and the sum is a separate op, so each is rounded on its own in that dtype. A zero
@@ -363,4 +398,4 @@ def mg_cycle_reference(u: torch.Tensor, f: torch.Tensor, weights_per_level, bc, 
 
 
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "box_step_reference", "axpby_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "box_step_reference", "varcoef_step_reference", "axpby_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]

@@ -70,7 +70,8 @@ int main(int argc, char **argv) {
                              "reductions beside the single-step sweep) or 'bc' (boundary fill beside the periodic exchange) or "
                              "'axpby' (field algebra beside the field reductions) or 'transfer' (grid transfer n^3 <-> (n/2)^3 "
                              "beside the one-operand reduction and the one-source axpby) or 'varcoef' (the "
-                             "variable-coefficient stencil beside the radius-1 star at n^3 and (n/2)^3, fp32 and fp64)");
+                             "variable-coefficient stencil beside the radius-1 star at n^3 and (n/2)^3, fp32 and fp64) or 'relax' (the "
+                             "fused variable-coefficient residual / Jacobi sweep beside varcoef and varcoef + axpby)");
   if (!p.parse(argc, argv)) return p.need_help() ? 0 : 1;
   std::setvbuf(stdout, nullptr, _IOLBF, 0); // progress lines reach a redirected log as they are printed
   LocalDomain ld(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
@@ -504,6 +505,59 @@ int main(int argc, char **argv) {
                       mcells * 3 * es / usv / 1e6, vi.path);
         }
       }
+  }
+  if (only == "relax") {
+    // The fused residual / Jacobi sweep of the variable-coefficient operator beside what it replaces, on one domain
+    // with the quantities u, kappa, f, r, interleaved per repetition, fp32 and fp64 at n^3: (a) stencil_varcoef_apply
+    // (three fields), (b) stencil_varcoef_apply then field_axpby r = f - next(u), the unfused residual (six fields), (c)
+    // relax in Residual mode into r and (d) in Jacobi mode into next(u) (four fields each). eff_TBps counts those fields.
+    VarCoefWeights vw; // 1 - div(kappa grad), kappa = 1.5: the diagonal is 10
+    vw.shift = 1.0;
+    vw.h[0] = vw.h[1] = vw.h[2] = -0.5;
+    for (int f64 = 0; f64 < 2; ++f64) {
+      const double es = f64 ? 8 : 4;
+      LocalDomain lv(Dim3(n, n, n), Dim3(0, 0, 0), 0, Backend::Device);
+      lv.set_radius(Radius::face_edge_corner(1, 0, 0));
+      for (const char *name : {"u", "kappa", "f", "r"}) {
+        if (f64)
+          lv.add_data<double>(name);
+        else
+          lv.add_data<float>(name);
+      }
+      lv.realize();
+      fill_value(lv, 0, 0.5, true, s);
+      fill_value(lv, 1, 1.5, true, s);
+      fill_value(lv, 2, 0.25, true, s);
+      s.sync();
+      const Rect3 regv = lv.get_compute_region();
+      char tag[32];
+      std::snprintf(tag, sizeof tag, "%s_%lld", f64 ? "fp64" : "fp32", (long long)n);
+      for (int rep = 0; rep < reps; ++rep) {
+        StencilTune t;
+        const VarCoefLaunchInfo vi = stencil_varcoef_launch_info(lv, 0, 1, regv, vw, t);
+        const VarCoefRelaxLaunchInfo ri =
+            stencil_varcoef_relax_launch_info(lv, 0, 1, 2, 3, true, regv, vw, VarCoefRelaxMode::Residual, t);
+        const double usa = timeit([&] { stencil_varcoef_apply(lv, 0, 1, regv, vw, s, t); });
+        const double usp = timeit([&] {
+          stencil_varcoef_apply(lv, 0, 1, regv, vw, s, t);
+          field_axpby_enqueue(lv, FieldRef(3, true), 1.0, FieldRef(2, true), -1.0, FieldRef(0, false), regv, s);
+        });
+        const double usr = timeit(
+            [&] { stencil_varcoef_relax(lv, 0, 1, 2, 3, true, regv, vw, VarCoefRelaxMode::Residual, 1.0, s, t); });
+        const double usj = timeit([&] {
+          stencil_varcoef_relax(lv, 0, 1, 2, 0, false, regv, vw, VarCoefRelaxMode::Jacobi, 6.0 / 7.0, s, t);
+        });
+        std::printf("stencil_varcoef,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", tag, vi.zchunk, usa, cells / usa / 1e3,
+                    cells * 3 * es / usa / 1e6, vi.path);
+        std::printf("varcoef_then_axpby,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", tag, vi.zchunk, usp, cells / usp / 1e3,
+                    cells * 6 * es / usp / 1e6, vi.path);
+        std::printf("varcoef_relax_residual,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", tag, ri.zchunk, usr, cells / usr / 1e3,
+                    cells * 4 * es / usr / 1e6, ri.path);
+        std::printf("varcoef_relax_jacobi,%s,2,%d,%.2f,%.1f,%.3f,path%d\n", tag, ri.zchunk, usj, cells / usj / 1e3,
+                    cells * 4 * es / usj / 1e6, ri.path);
+        std::printf("relax_ratios,%s,residual_over_pair,%.3f,jacobi_over_apply,%.3f\n", tag, usr / usp, usj / usa);
+      }
+    }
   }
   if (only == "bc") {
     // Boundary fill beside the periodic exchange of the same domain (fp32, face radius 3, one GPU): (a) the exchange

@@ -467,6 +467,34 @@ struct VarCoefLaunchInfo {
 VarCoefLaunchInfo stencil_varcoef_launch_info(const LocalDomain &dom, int64_t qu, int64_t qk, const Rect3 &region,
                                               const VarCoefWeights &w, const StencilTune &tune = StencilTune());
 
+// Residual and damped-Jacobi sweep of the operator above (stencil_varcoef_relax.hip): for quantities u, k and f of one
+// element type T and row pitch in one LocalDomain and a destination buffer dst
+//   acc exactly as stencil_varcoef_apply; dg = shift; for axis x, y, z, low face then high face:
+//     ks = k(c) + k(n) (the sum acc uses); g = h[axis] * ks; dg = dg - g
+//   r = f(c) - acc
+//   Residual: dst(c) = r          Jacobi: q = r / dg; s = omega_T * q; dst(c) = u(c) + s
+// with shift, h and omega converted to T once on the host and every sum, difference, product and quotient its own IEEE
+// rounding in T (no FMA contraction, a true division; dg = 0 is not special: +-inf and NaN propagate). dg is the
+// diagonal of the operator at the cell. Bitwise equal to stencil2_amd.ops.varcoef_relax_reference.
+enum class VarCoefRelaxMode { Residual, Jacobi };
+// fp32 / fp64 quantities (or opaque 4- / 8-byte elements) of one element size and row pitch in a realized domain
+// whose six face radii are >= 1
+bool stencil_varcoef_relax_supported(const LocalDomain &dom, int64_t qu, int64_t qk, int64_t qf, int64_t qdst);
+// dst(region) = the update above from curr(u), curr(k) and curr(f); dst is the curr (dstCurr) or next buffer of
+// quantity qdst, and only its cells of `region` are written. dst must not be curr(u) or curr(k), whose neighbours are
+// read (refused); it may be curr(f): a cell's f is read only by the lane that stores that cell, before the store. The
+// three paths, the halos needed and `tune` are those of stencil_varcoef_apply; the z-march reads f at the centre only
+// and carries the diagonal's share of the face behind beside the face term.
+void stencil_varcoef_relax(const LocalDomain &dom, int64_t qu, int64_t qk, int64_t qf, int64_t qdst, bool dstCurr,
+                           const Rect3 &region, const VarCoefWeights &w, VarCoefRelaxMode mode, double omega,
+                           hipStream_t stream, const StencilTune &tune = StencilTune());
+// What stencil_varcoef_relax would run for these arguments (nothing is launched; the same refusals raise)
+using VarCoefRelaxLaunchInfo = VarCoefLaunchInfo;
+VarCoefRelaxLaunchInfo stencil_varcoef_relax_launch_info(const LocalDomain &dom, int64_t qu, int64_t qk, int64_t qf,
+                                                         int64_t qdst, bool dstCurr, const Rect3 &region,
+                                                         const VarCoefWeights &w, VarCoefRelaxMode mode,
+                                                         const StencilTune &tune = StencilTune());
+
 // Jacobi init: curr = 0.5 on `region` (reference bin/jacobi3d.cu:18-29)
 void jacobi_init(const LocalDomain &dom, int64_t qi, const Rect3 &region, hipStream_t stream);
 // Astaroth init: interior = sin(2*pi/period*(origin+x+y+z)) (x,y,z raw indices), halo = -10 (astaroth_sim.cu:14-61)

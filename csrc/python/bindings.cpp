@@ -1161,6 +1161,39 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"), py::arg("region"), py::arg("weights"),
         py::arg("tune"));
+  m.def("stencil_varcoef_relax_supported",
+        [](DistributedDomain &dd, size_t di, int64_t qu, int64_t qk, int64_t qf, int64_t qdst) {
+          return stencil_varcoef_relax_supported(dd.domains().at(di), qu, qk, qf, qdst);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"), py::arg("qf"), py::arg("qdst"));
+  m.def("stencil_varcoef_relax",
+        [](DistributedDomain &dd, size_t di, int64_t qu, int64_t qk, int64_t qf, int64_t qdst, bool dstCurr,
+           const Rect3 &region, const VarCoefWeights &w, bool jacobi, double omega, uintptr_t stream,
+           const StencilTune &tune) {
+          stencil_varcoef_relax(dd.domains().at(di), qu, qk, qf, qdst, dstCurr, region, w,
+                                jacobi ? VarCoefRelaxMode::Jacobi : VarCoefRelaxMode::Residual, omega,
+                                reinterpret_cast<hipStream_t>(stream), tune);
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"), py::arg("qf"), py::arg("qdst"),
+        py::arg("dst_curr"), py::arg("region"), py::arg("weights"), py::arg("jacobi"), py::arg("omega"),
+        py::arg("stream"), py::arg("tune"), py::call_guard<py::gil_scoped_release>());
+  m.def("stencil_varcoef_relax_launch_info",
+        [](DistributedDomain &dd, size_t di, int64_t qu, int64_t qk, int64_t qf, int64_t qdst, bool dstCurr,
+           const Rect3 &region, const VarCoefWeights &w, bool jacobi, const StencilTune &tune) {
+          // what stencil_varcoef_relax would run (nothing is launched)
+          const VarCoefRelaxLaunchInfo r = stencil_varcoef_relax_launch_info(
+              dd.domains().at(di), qu, qk, qf, qdst, dstCurr, region, w,
+              jacobi ? VarCoefRelaxMode::Jacobi : VarCoefRelaxMode::Residual, tune);
+          static const char *names[] = {"none", "host", "generic", "fast"};
+          py::dict o;
+          o["path"] = names[r.path + 1];
+          o["zchunk"] = r.zchunk;
+          o["zchunks"] = r.zchunks;
+          o["blocks"] = r.blocks;
+          return o;
+        },
+        py::arg("dd"), py::arg("domain"), py::arg("qu"), py::arg("qk"), py::arg("qf"), py::arg("qdst"),
+        py::arg("dst_curr"), py::arg("region"), py::arg("weights"), py::arg("jacobi"), py::arg("tune"));
   // ---------------- boundary fill ----------------
   auto fill_requests =[](const std::vector<int64_t> &qs, const std::vector<BoundaryConditions> &bcs, bool curr) {
     STENCIL_REQUIRE(qs.size() == bcs.size(), "boundary fill: " << qs.size() << " quantities, " << bcs.size() << " conditions");

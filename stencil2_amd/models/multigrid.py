@@ -18,6 +18,17 @@ The levels are decided from numbers every rank knows (the global size and the pa
 is partitioned over the same GPUs; there is no agglomeration of coarse levels onto fewer GPUs, so a decomposition
 into thin slabs stops coarsening early and leans on ``coarse_sweeps``.
 
+With ``VarCoefWeights`` (``ops.operator_varcoef``) and ``kappa=fn`` A is the variable-coefficient operator of
+``ops.varcoef_apply``, whose diagonal differs per cell. Every level then has two more quantities after u, f and r: the
+coefficient kappa and a second iterate v with u's conditions. Level 0's kappa is ``fn``, level l + 1's the 8-cell mean
+(``ops.restrict_apply``) of level l's, each given its halos and ghost cells once (``kappa_boundary``; None = Mirror on
+every non-periodic face of ``boundary``). A smoothing sweep is the halo fill and one ``ops.varcoef_relax`` launch per
+sub-domain (u + omega (f - A u) / diag(A) in one pass over u, kappa and f), sweeps alternating between u and v; the
+residual is the same kernel in residual mode, its norm ``DistributedDomain.reduce``. Level l uses shift and h / 4^l.
+Arithmetic-mean coarse coefficients keep the cycle's factor near the constant-coefficient one for smooth kappa and
+moderate random kappa; sharp jumps slow it down (harmonic or Galerkin coarse operators are not provided), and
+``StarCG`` remains the robust choice there.
+
 Singular operators (a periodic or all-Mirror Laplacian with no centre shift) are the caller's responsibility, as in
 ``StarCG``.
 """
@@ -29,10 +40,11 @@ import torch
 
 from .. import _C
 from ..ops.kernels import (box_apply, box_supported, field_axpby_supported, grid_transfer_supported, prolong_apply,
-                           restrict_apply, star_apply, star_supported)
+                           restrict_apply, star_apply, star_supported, varcoef_relax, varcoef_relax_supported)
 from ..ops.multigrid import coarsened_weights, smoother_weights, weights_center
 from ..parallel.domain import DistributedDomain
 from .star_cg import _AXES, _conditions
+from .varcoef_model import kappa_conditions, refuse_open
 
 
 def plan_levels(size, dim, R: int, min_size: int = 4, max_levels=None):
@@ -59,10 +71,19 @@ def plan_levels(size, dim, R: int, min_size: int = 4, max_levels=None):
 class StarMG:
     def __init__(self, size, weights, fp64: bool = True, gpus=None, backend=None, methods=_C.MethodFlags.All,
                  group=None, boundary=None, nu=(2, 2), omega: float = 6.0 / 7.0, coarse_sweeps: int = 32,
-                 max_levels=None, min_size: int = 4):
+                 max_levels=None, min_size: int = 4, kappa=None, kappa_boundary=None):
         w0 = weights(0) if callable(weights) else weights
         self._box = isinstance(w0, _C.BoxWeights)
-        R = 1 if self._box else w0.radius
+        self._varcoef = isinstance(w0, _C.VarCoefWeights)
+        if self._varcoef and kappa is None:
+            raise ValueError("StarMG on VarCoefWeights needs the coefficient: kappa=fn(gz, gy, gx)")
+        if not self._varcoef and (kappa is not None or kappa_boundary is not None):
+            raise ValueError(f"kappa= / kappa_boundary= belong to VarCoefWeights, not {type(w0).__name__}")
+        if self._varcoef:
+            if boundary is None and kappa_boundary is not None:
+                raise ValueError("kappa_boundary needs boundary: the periodic faces of u and kappa are the grid's")
+            refuse_open(kappa_boundary, "StarMG (kappa)")
+        R = 1 if self._box or self._varcoef else w0.radius
         if R not in (1, 2, 3):
             raise ValueError(f"star radius must be 1, 2 or 3, not {R}")
         if boundary is not None:
@@ -73,6 +94,8 @@ class StarMG:
         if max_levels is not None and max_levels < 2:
             raise ValueError(f"StarMG needs at least two levels, max_levels = {max_levels}")
         self.boundary = boundary
+        self.kappa_boundary = kappa_conditions(boundary, kappa_boundary) if self._varcoef else None
+        self.kappa = self.v = None
         self.dtype = torch.float64 if fp64 else torch.float32
         self.nu = (int(nu[0]), int(nu[1]))
         self.omega = float(omega)
@@ -95,6 +118,14 @@ class StarMG:
                                 for l in range(1, len(sizes))]
         self._c, self._smoother = [], []
         for l, w in enumerate(self._weights):
+            if self._varcoef or isinstance(w, _C.VarCoefWeights):
+                if not (self._varcoef and isinstance(w, _C.VarCoefWeights)):
+                    raise ValueError(f"the weights of level {l} differ in kind or radius from level 0")
+                dd = self._dds[l]
+                for di in range(dd.num_domains()):
+                    assert all(varcoef_relax_supported(dd, di, self.u, self.kappa, self.f, q)
+                               for q in (self.v, self.u, self.r))
+                continue
             if isinstance(w, _C.BoxWeights) != self._box or (not self._box and w.radius != R):
                 raise ValueError(f"the weights of level {l} differ in kind or radius from level 0")
             c = self.omega / weights_center(w)
@@ -106,9 +137,11 @@ class StarMG:
                 assert ok and field_axpby_supported(dd, di, self.r, self.f, self.u)
         self.history = []
         for l in range(len(sizes)):
-            for q in (self.u, self.f, self.r):
+            for q in (self.u, self.f, self.r) + ((self.v,) if self._varcoef else ()):
                 self._zero(l, q)
         self.synchronize()
+        if self._varcoef:
+            self.set_kappa(kappa)
 
     # ---- levels ----
     def _make_level(self, size, level):
@@ -122,10 +155,16 @@ class StarMG:
         if cfg["backend"] is not None:
             dd.set_backend(cfg["backend"])
         self.u, self.f, self.r = (dd.add_data(n, self.dtype) for n in ("u", "f", "r"))
+        if self._varcoef:
+            # after u, f and r, whose indices are the same for every kind of weights
+            self.kappa, self.v = (dd.add_data(n, self.dtype) for n in ("kappa", "v"))
         if self.boundary is not None:
+            # the default conditions: u, and the second iterate v
             dd.set_boundary_conditions(self.boundary if level == 0 else _conditions(self.boundary, True))
             for q in (self.r, self.f):
                 dd.set_boundary_conditions(q, _conditions(self.boundary, False, all_open=True))
+            if self._varcoef:
+                dd.set_boundary_conditions(self.kappa, self.kappa_boundary)
         dd.realize()
         return dd
 
@@ -169,6 +208,27 @@ class StarMG:
         self._dds[0].fill_from_global(self.f, fn)
         return self
 
+    def set_kappa(self, fn):
+        """kappa = fn(gz, gy, gx) at level 0 and its 8-cell means on the coarser levels, then every level's halos and
+        ghost cells of kappa, once: no kernel of the cycle writes curr(kappa) (VarCoefWeights only)"""
+        if not self._varcoef:
+            raise ValueError("set_kappa belongs to VarCoefWeights")
+        self._dds[0].fill_from_global(self.kappa, fn)
+        for l in range(1, self.levels):
+            fine, coarse = self._dds[l - 1], self._dds[l]
+            for di in range(fine.num_domains()):
+                restrict_apply(fine, coarse, di, self.kappa, self.kappa)
+        for dd in self._dds:
+            dd.exchange()
+            if self.boundary is not None:
+                dd.apply_boundary(self.kappa)
+        return self
+
+    def level_kappa(self, l: int, di: int = 0) -> torch.Tensor:
+        """interior (z, y, x) view of the coefficient on local sub-domain di of level l (VarCoefWeights only)"""
+        dd = self._dds[l]
+        return dd.interior(dd.curr(di, self.kappa), di)
+
     def set_guess(self, fn=None):
         """u0 = fn(gz, gy, gx); default 0"""
         if fn is None:
@@ -187,13 +247,13 @@ class StarMG:
             torch.cuda.synchronize()
 
     # ---- the cycle ----
-    def _halos(self, l):
-        """valid halos of curr(u) at level l: the exchange (blocking; it orders itself after the null stream, where the
-        kernels run), then the ghost cells beyond the walls"""
+    def _halos(self, l, q=None):
+        """valid halos of curr(q) (default u) at level l: the exchange (blocking; it orders itself after the null
+        stream, where the kernels run), then the ghost cells beyond the walls"""
         dd = self._dds[l]
         dd.exchange()
         if self.boundary is not None:
-            dd.apply_boundary(self.u)
+            dd.apply_boundary(self.u if q is None else q)
 
     def _apply(self, l, weights):
         """next(u) = weights applied to curr(u) at level l"""
@@ -208,12 +268,30 @@ class StarMG:
     def _smooth(self, l, sweeps):
         """damped Jacobi: u <- (I - c A) u + c f, c = omega / centre(A)"""
         dd = self._dds[l]
+        if self._varcoef:
+            # u + omega (f - A u) / diag(A) in one pass, ping-pong between u and v; an odd count ends with one copy
+            src, dst = self.u, self.v
+            for _ in range(sweeps):
+                self._halos(l, src)
+                for di in range(dd.num_domains()):
+                    varcoef_relax(dd, di, src, self.kappa, self.f, self._weights[l], omega=self.omega, dst=dst,
+                                  dst_curr=True)
+                src, dst = dst, src
+            if sweeps % 2:
+                dd.copy(self.u, self.v)
+            return
         for _ in range(sweeps):
             self._apply(l, self._smoother[l])
             dd.axpby(self.u, 1.0, self.u, self._c[l], self.f, x_curr=False)
 
     def _residual(self, l, stats=False):
         """r = f - A u at level l; with stats the FieldStats of r (collective)"""
+        if self._varcoef:
+            dd = self._dds[l]
+            self._halos(l)
+            for di in range(dd.num_domains()):
+                varcoef_relax(dd, di, self.u, self.kappa, self.f, self._weights[l], dst=self.r, dst_curr=True)
+            return dd.reduce(self.r) if stats else None
         self._apply(l, self._weights[l])
         return self._dds[l].axpby(self.r, 1.0, self.f, -1.0, self.u, y_curr=False, stats=stats)
 

@@ -322,6 +322,47 @@ def varcoef_launch_info(dd, di: int, q: int, kappa: int, w, region=None, tune=No
     return _C.stencil_varcoef_launch_info(native, di, int(q), int(kappa), region, w, _tune(tune))
 
 
+def _relax_dst(q, dst):
+    return int(q) if dst is None else int(dst)
+
+
+def varcoef_relax_supported(dd, di: int, q: int, kappa: int, f: int, dst=None) -> bool:
+    """True when `varcoef_relax` can run on quantity q with the coefficient `kappa`, the right-hand side `f` and the
+    destination quantity `dst` (default q) of local sub-domain di: fp32 / fp64 quantities (or opaque 4- / 8-byte
+    elements) of one element size and row pitch, and all six face radii of the domain >= 1."""
+    return _C.stencil_varcoef_relax_supported(getattr(dd, "native", dd), di, int(q), int(kappa), int(f),
+                                              _relax_dst(q, dst))
+
+
+def varcoef_relax(dd, di: int, q: int, kappa: int, f: int, w, omega=None, dst=None, dst_curr: bool = False, region=None,
+                  stream: int = 0, tune=None):
+    """One pass over u = curr(q), curr(kappa) and curr(f) of local sub-domain di with A the operator of
+    `varcoef_apply` for `w`: omega=None stores the residual f - A u, otherwise the damped-Jacobi update
+    u + omega * ((f - A u) / diag(A)), diag(A) = w.shift - sum over the six faces of w.h[axis] * (kappa(c) + kappa(n)).
+    The destination is the next (or, with dst_curr, the curr) buffer of quantity `dst` (default q, so the default
+    writes next(q)); only its cells of `region` (default the compute region) are written. curr(q) and curr(kappa)
+    are refused as destination, curr(f) is allowed. The face halos of curr(q) and curr(kappa) must be valid to depth 1.
+    Every sum, difference, product and quotient is its own rounding in the quantities' type, in the order of
+    `varcoef_relax_reference`, so the result is bitwise equal to it (a zero diagonal gives inf / NaN). `tune` as for
+    `varcoef_apply` (csrc/src/kernels/stencil_varcoef_relax.hip)."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    _C.stencil_varcoef_relax(native, di, int(q), int(kappa), int(f), _relax_dst(q, dst), bool(dst_curr), region, w,
+                             omega is not None, 1.0 if omega is None else float(omega), stream, _tune(tune))
+
+
+def varcoef_relax_launch_info(dd, di: int, q: int, kappa: int, f: int, w, omega=None, dst=None, dst_curr: bool = False,
+                              region=None, tune=None) -> dict:
+    """What `varcoef_relax` would run for these arguments (nothing is launched; the same refusals raise): `path`,
+    `zchunk`, `zchunks`, `blocks` as `varcoef_launch_info`."""
+    native = getattr(dd, "native", dd)
+    if region is None:
+        region = native.domain(di).get_compute_region()
+    return _C.stencil_varcoef_relax_launch_info(native, di, int(q), int(kappa), int(f), _relax_dst(q, dst),
+                                                bool(dst_curr), region, w, omega is not None, _tune(tune))
+
+
 def _native(dd):
     return getattr(dd, "native", dd)
 

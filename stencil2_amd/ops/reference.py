@@ -198,6 +198,50 @@ def varcoef_step_reference(u: torch.Tensor, kappa: torch.Tensor, w, boundary=Non
     return acc
 
 
+def varcoef_relax_reference(u: torch.Tensor, kappa: torch.Tensor, f: torch.Tensor, w, omega=None, boundary=None,
+                            kappa_boundary=None) -> torch.Tensor:
+    """The residual (omega None) or one damped-Jacobi sweep of the variable-coefficient operator on global (z, y, x)
+    grids: the oracle of `varcoef_relax`. acc as `varcoef_step_reference`, and beside it dg = shift, then per axis
+    x, y, z first the low face, then the high face: ks = kappa + kappa(n) (the sum acc uses); g = h[axis] * ks;
+    dg = dg - g. r = f - acc; the residual is r, the sweep q = r / dg; s = omega * q; u + s. shift, h and omega are
+    0-dim tensors of u's dtype (one conversion from double) and every sum, difference, product and quotient is a
+    separate op on tensors, so each is rounded on its own in that dtype (the quotient is a true division: the divisor
+    is a tensor). `boundary` / `kappa_boundary` as in `varcoef_step_reference`."""
+    def wt(v):
+        return torch.tensor(v, dtype=torch.float64).to(u.dtype).to(u.device)
+
+    def neighbours(g, bc):
+        if bc is None:
+            return lambda k, dim: torch.roll(g, k, dim)  # g(c - k e)
+        p = pad_reference(g, 1, bc)
+        Z, Y, X = g.shape
+
+        def nb(k, dim):
+            lo = [1, 1, 1]
+            lo[dim] -= k
+            return p[lo[0]:lo[0] + Z, lo[1]:lo[1] + Y, lo[2]:lo[2] + X]
+        return nb
+
+    un, kn = neighbours(u, boundary), neighbours(kappa, kappa_boundary)
+    h = list(w.h)
+    acc = wt(w.shift) * u
+    dg = torch.zeros_like(u) + wt(w.shift)
+    for ax, dim in enumerate((2, 1, 0)):
+        for k in (1, -1):  # c - e, then c + e
+            ks = kappa + kn(k, dim)
+            d = un(k, dim) - u
+            t = wt(h[ax]) * (ks * d)
+            acc = acc + t
+            g = wt(h[ax]) * ks
+            dg = dg - g
+    r = f - acc
+    if omega is None:
+        return r
+    q = r / dg
+    s = wt(float(omega)) * q
+    return u + s
+
+
 def axpby_reference(a, x: torch.Tensor, b=None, y=None) -> torch.Tensor:
     """a * x, or a * x + b * y: the oracle of `field_axpby`. a and b are 0-dim tensors of x's dtype (one conversion
     from double), and each product and the sum is a separate op, so each is rounded on its own in that dtype. A zero
@@ -397,5 +441,41 @@ def mg_cycle_reference(u: torch.Tensor, f: torch.Tensor, weights_per_level, bc, 
     return cycle(0, u, f, bc)
 
 
+def varcoef_mg_cycle_reference(u: torch.Tensor, f: torch.Tensor, kappa: torch.Tensor, weights_per_level, bc,
+                               kappa_bc=None, nu=(2, 2), omega: float = 6.0 / 7.0, coarse_sweeps: int = 32) -> torch.Tensor:
+    """One V-cycle of `models.StarMG` on `VarCoefWeights`, on gathered global (z, y, x) grids with the same scalars in
+    the same order: the oracle of `StarMG.cycle` for the variable-coefficient operator. `weights_per_level[l]` is the
+    VarCoefWeights of level l; kappa of level l + 1 is `restrict_reference` of level l's; `bc` the conditions of u at
+    level 0 (None: periodic), coarser levels take its homogeneous twin; every level's kappa is padded with `kappa_bc`
+    (None with walls: Mirror on every non-periodic face of `bc`). A smoothing sweep is `varcoef_relax_reference` with
+    `omega`, the residual the same with omega None; the coarse problem starts from 0 and the coarsest level runs
+    `coarse_sweeps` sweeps. Returns u after the cycle."""
+    from ..models.star_cg import _conditions
+    from ..models.varcoef_model import kappa_conditions
+
+    hom = None if bc is None else _conditions(bc, True)
+    kbc = None if bc is None else kappa_conditions(bc, kappa_bc)
+    last = len(weights_per_level) - 1
+
+    def cycle(level, u, f, kappa, cond):
+        A = weights_per_level[level]
+
+        def smooth(u, sweeps):
+            for _ in range(sweeps):
+                u = varcoef_relax_reference(u, kappa, f, A, omega=omega, boundary=cond, kappa_boundary=kbc)
+            return u
+
+        if level == last:
+            return smooth(u, coarse_sweeps)
+        u = smooth(u, nu[0])
+        r = varcoef_relax_reference(u, kappa, f, A, boundary=cond, kappa_boundary=kbc)
+        rc = restrict_reference(r)
+        e = cycle(level + 1, torch.zeros_like(rc), rc, restrict_reference(kappa), hom)
+        u = prolong_reference(e, boundary=hom, add=u)
+        return smooth(u, nu[1])
+
+    return cycle(0, u, f, kappa, bc)
+
+
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "box_step_reference", "varcoef_step_reference", "axpby_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "box_step_reference", "varcoef_step_reference", "varcoef_relax_reference", "varcoef_mg_cycle_reference", "axpby_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]

@@ -87,6 +87,9 @@ struct StencilTune {
   // z chunk (true) or through the thin slab kernel (false); both time the same within 2 % (r2s3)
   bool zslabRow = true;
   bool xcdRemap = true;
+  // nontemporal output stores. Fused triples: the whole-row kernel compiles an instance per setting (512^3: 1828-1849
+  // Gcells/s with, 1783-1797 without, BASELINE.md "Deferred output stores"); in the XH form (columns with x halos)
+  // and in the publishing instances the flag does nothing, their stores are plain
   bool nontemporal = true;
   // reverse the z-march of every block on odd buffer parities: each step then starts on the planes the previous
   // step wrote last, which are still in the MALL / L2
@@ -170,6 +173,10 @@ struct X3PlanInfo {
   std::vector<int> zb;     // per lockstep group its parts - 1 z bounds (empty: equal parts)
   std::vector<int> l0, l1; // per block: its leftover slice
   std::vector<int> odd;    // per block: the slice's march direction bit
+  // every march of the sweep in the order its block runs them, five ints each: block, row group, first plane, planes,
+  // marching down (at sweep parity 0; StencilTune::alternateZ flips every direction on odd sweeps). A march of n
+  // planes runs n + 4 z steps
+  std::vector<int> marches;
 };
 X3PlanInfo stencil7x3_plan(const Dim3 &size, bool jacobi, const StencilTune &tune, int slots = 256);
 // dst(region) = stencil(src) for one quantity of one LocalDomain. `region` is in global coordinates and must lie in

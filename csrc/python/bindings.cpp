@@ -1243,7 +1243,8 @@ PYBIND11_MODULE(_C, m) {
       .def_readonly("zb", &X3PlanInfo::zb)
       .def_readonly("l0", &X3PlanInfo::l0)
       .def_readonly("l1", &X3PlanInfo::l1)
-      .def_readonly("odd", &X3PlanInfo::odd);
+      .def_readonly("odd", &X3PlanInfo::odd)
+      .def_readonly("marches", &X3PlanInfo::marches);
   m.def(
       "stencil7x3_plan",
       [](py::handle size, bool jacobi, py::object tune, int slots) {

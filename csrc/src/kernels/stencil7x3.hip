@@ -58,8 +58,8 @@ struct X3Seg {
   bool odd2; // the second's
 };
 template <typename T>
-__device__ __forceinline__ X3Seg x3_segments(const StencilArgs<T> &a, const ZPartBounds &B, uint32_t lb, uint32_t nb,
-                                             uint32_t ncols, uint32_t gy, uint32_t nzt) {
+__host__ __device__ __forceinline__ X3Seg x3_segments(const StencilArgs<T> &a, const ZPartBounds &B, uint32_t lb,
+                                                      uint32_t nb, uint32_t ncols, uint32_t gy, uint32_t nzt) {
   X3Seg r{0, 0, 0, 0, false, false};
   if (a.seg == 3) { // rounds of whole column groups (x3_round): parts alternate their z direction as in seg 2
     r.odd = ((lb / (nb / uint32_t(a.zparts))) & 1) != 0;
@@ -456,7 +456,11 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
               row_update(U2c, A, B, DOWN ? U2b : U2a, DOWN ? U2a : U2b, XH ? ev[buf][w][side] : T(0), o);
               sphere_row(row_sph(z), o);
               // unconditional: a row past the region's y end (the last row group) stores into a per-device sink, so
-              // every path has the same vector-memory ops and the next step's load wait counts past these stores
+              // every path has the same vector-memory ops. The next step's load wait does not count past these
+              // stores: it is vmcnt(3) / (2) with that step's two loads issued behind them, so it also waits for the
+              // stores to be acknowledged (storing a step later, behind that wait, measured slower: BASELINE.md,
+              // "Deferred output stores"). a.nt does nothing here: the compiler merges the two stores below into one
+              // plain store (no triple kernel of this form holds a nontemporal store)
               if constexpr (!RAG) {
                 char *dp = outRow ? reinterpret_cast<char *>(a.dst + int64_t(z) * a.pxy) + outoff
                                   : a.sink + lane * V * int(sizeof(T));
@@ -604,8 +608,9 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
 
 // Whole periodic rows (fp32, 512 cells, x wrapped in-kernel): x-neighbours and the wrap by DPP lane rotates of the
 // wave's own registers; the headline kernel (bench.py, one GPU). Kept apart from the XH form: sharing one body cost
-// the whole-row instance ~3 % more VALU (window register moves) and 1.2 % of steady-state time (profiles/r6/r6n)
-template <int KIND, bool PUB>
+// the whole-row instance ~3 % more VALU (window register moves) and 1.2 % of steady-state time (profiles/r6/r6n).
+// NT: the output is stored nontemporal (StencilTune::nontemporal; the publishing instances keep plain stores)
+template <int KIND, bool PUB, bool NT>
 __global__ __launch_bounds__(64 * 12, 3) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
   constexpr int NW = 12;     // 3 waves per SIMD (168 VGPRs), 3 x 48 KiB of LDS
@@ -815,13 +820,18 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
             levels();
             if constexpr (LV >= 3) {
               // unconditional: a row past the region's y end (the last row group) stores into a per-device sink, so
-              // every path has the same vector-memory ops and the next step's load wait counts past these stores
+              // every path has the same vector-memory ops. The next step's load wait does not count past these
+              // stores: it is vmcnt(3) / (2) with that step's two loads issued behind them, so it also waits for the
+              // stores to be acknowledged (storing a step later, behind that wait, measured slower: BASELINE.md,
+              // "Deferred output stores")
               char *dp = outRow ? reinterpret_cast<char *>(a.dst + int64_t(z) * a.pxy) + outoff
                                 : a.sink + lane * LS * int(sizeof(T));
 #pragma unroll
               for (int h = 0; h < H; ++h) {
                 NV *q = reinterpret_cast<NV *>(dp + h * CS * int(sizeof(T)));
-                if (a.nt)
+                // NT is a template parameter: as a run-time choice (a.nt ? nontemporal : plain) the compiler merged
+                // the two stores into one plain store, and StencilTune::nontemporal did nothing in this kernel
+                if constexpr (NT)
                   __builtin_nontemporal_store(o[h], q);
                 else
                   *q = o[h];
@@ -896,9 +906,10 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
 
 // ---------------------------------------------------------------------------------------------------------
 // host side
-template <typename T, int KIND> static const void *x3_wrap_kernel_ptr() {
+template <typename T, int KIND> static const void *x3_wrap_kernel_ptr(bool nt) {
   if constexpr (std::is_same<T, float>::value)
-    return (const void *)stencil7x3_wrap_kernel<KIND, false>;
+    return nt ? (const void *)stencil7x3_wrap_kernel<KIND, false, true>
+              : (const void *)stencil7x3_wrap_kernel<KIND, false, false>;
   else
     return nullptr;
 }
@@ -1127,7 +1138,8 @@ static X3Launch<T> x3_prepare(const LocalDomain &dom, int64_t qi, const Rect3 &r
   const bool rag = XH && a.xr < cw;
   a.gy = (ny + YO - 1) / YO;
   const bool big = dom.buffer_bytes(qi) >= (int64_t(1) << 32) - 4096;
-  const void *kern = XH ? (const void *)x3_xh_kernel_ptr<T, KIND>(big, false, rag) : x3_wrap_kernel_ptr<T, KIND>();
+  const void *kern =
+      XH ? (const void *)x3_xh_kernel_ptr<T, KIND>(big, false, rag) : x3_wrap_kernel_ptr<T, KIND>(a.nt != 0);
   const int64_t cols = int64_t(a.gx) * a.gy;
   const int64_t resident = resident_blocks(kern, 64 * NW, 1);
   // CUs left to the transport kernels running beside the sweep (pipelined triples: the gated exchange)
@@ -1189,11 +1201,41 @@ static void apply_x3_t(const LocalDomain &dom, int64_t qi, const Rect3 &region, 
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64, NW), 0, stream, a, zb);
   } else {
     if (a.pub)
-      hipLaunchKernelGGL((stencil7x3_wrap_kernel<KIND, true>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
+      hipLaunchKernelGGL((stencil7x3_wrap_kernel<KIND, true, false>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
+    else if (a.nt)
+      hipLaunchKernelGGL((stencil7x3_wrap_kernel<KIND, false, true>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
     else
-      hipLaunchKernelGGL((stencil7x3_wrap_kernel<KIND, false>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
+      hipLaunchKernelGGL((stencil7x3_wrap_kernel<KIND, false, false>), dim3(blocks), dim3(64, NW), 0, stream, a, zb);
   }
   HIP_CHECK(hipGetLastError());
+}
+
+// the marches of every block of a whole-row sweep in the order stencil7x3_wrap_kernel (not publishing) runs them: the
+// kernel's pass and segment loops over x3_segments on the host. Five ints per march (X3PlanInfo::marches)
+static std::vector<int> x3_marches(const StencilArgs<float> &a, const ZPartBounds &zb, uint32_t nb) {
+  constexpr int YO = 6;
+  std::vector<int> out;
+  const uint32_t nzt = uint32_t(a.hiz - a.loz);
+  for (uint32_t lb = 0; lb < nb; ++lb) {
+    const X3Seg sg = x3_segments(a, zb, lb, nb, uint32_t(a.gy), uint32_t(a.gy), nzt);
+    bool odd = sg.odd;
+    for (int pass = 0; pass < 2; ++pass) {
+      uint32_t s = pass == 0 ? sg.s : sg.s2;
+      const uint32_t e = pass == 0 ? sg.e : sg.e2;
+      if (pass == 1) odd = sg.odd2;
+      while (s < e) {
+        const uint32_t by = s / nzt;
+        const int zo = int(s - by * nzt);
+        const int nzs = int(std::min(nzt - uint32_t(zo), e - s));
+        s += uint32_t(nzs);
+        const bool down = odd != (a.flip != 0);
+        odd = !odd;
+        if (a.loy + YO * int(by) >= a.hiy) continue;
+        out.insert(out.end(), {int(lb), int(by), a.loz + zo, nzs, int(down)});
+      }
+    }
+  }
+  return out;
 }
 
 X3PlanInfo stencil7x3_plan(const Dim3 &size, bool jacobi, const StencilTune &tune, int slots) {
@@ -1222,9 +1264,15 @@ X3PlanInfo stencil7x3_plan(const Dim3 &size, bool jacobi, const StencilTune &tun
   r.parts = ls.parts;
   r.blocks = ls.seg == 1 ? 0 : int(ls.blocks);
   r.rounds = ls.rounds;
-  if (ls.seg != 2) return r;
+  a.seg = ls.seg;
+  if (ls.seg != 2) {
+    r.marches = x3_marches(a, ZPartBounds{}, uint32_t(ls.blocks));
+    return r;
+  }
   a.zparts = ls.parts;
   const X3Plan pl = x3_plan(a, jacobi, cols, slots, uint32_t(ls.blocks), tune);
+  a.zparts = pl.P;
+  r.marches = x3_marches(a, pl.b, pl.blocks);
   r.parts = pl.P;
   r.blocks = int(pl.blocks);
   r.lockstepGroups = int(pl.blocks) / pl.P;

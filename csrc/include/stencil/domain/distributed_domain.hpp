@@ -29,6 +29,7 @@
 #include "stencil/domain/packer.hpp"
 #include "stencil/kernels/boundary_fill.hpp"
 #include "stencil/kernels/field_axpby.hpp"
+#include "stencil/kernels/field_convert.hpp"
 #include "stencil/kernels/field_reduce.hpp"
 #include "stencil/kernels/stencil_ops.hpp"
 #include "stencil/rt/stream.hpp"
@@ -380,6 +381,11 @@ public:
   // The halos of dst are stale afterwards.
   FieldStats axpby(FieldRef dst, double a, FieldRef x, double b, FieldRef y, bool stats, bool local,
                    hipStream_t stream = nullptr);
+  // dst = T_dst(scale * double(src)) over the compute region of every local sub-domain, from quantity `src` of another
+  // domain with the same local partition (or of this one): stencil/kernels/field_convert.hpp. Refusals, `stats`,
+  // `local` and `stream` as in axpby; the stats are those of the values stored into this domain.
+  FieldStats convert_from(const DistributedDomain &srcDom, FieldRef dst, FieldRef src, double scale, bool stats,
+                          bool local, hipStream_t stream = nullptr);
 
   // ---- transport log (wait vs copy of the fused co-located kernels) ----
   // keep the last `exchanges` exchanges' device timestamps (s_memrealtime, 100-MHz constant clock) of every fused
@@ -469,6 +475,7 @@ private:
   // blocking receive (bounded by its own wait timeout).
   bool drain_ipc_acks(double timeout_s);
   bool x_face_lines(const LocalDomain &s, const LocalDomain &d) const; // translate s -> d copies x faces as lines
+  FieldStats merged_stats(bool local, hipStream_t stream); // of the scratches after axpby / convert_from with stats
   std::string planPrefix_ = "plan";
   int numaNode_ = -1; // NUMA node the calling thread was bound to in realize() (-1: none)
 

@@ -753,6 +753,61 @@ PYBIND11_MODULE(_C, m) {
         py::arg("curr_x"), py::arg("b"), py::arg("qy"), py::arg("curr_y"), py::arg("region"), py::arg("stats") = false,
         py::arg("max_blocks") = 0, py::arg("nontemporal") = false);
 
+  // ---------------- field conversion between two domains ----------------
+  {
+    auto sub = [](DistributedDomain &dd, size_t di) -> LocalDomain & {
+      STENCIL_REQUIRE(di < dd.domains().size(), "field convert: no local sub-domain " << di << " (" << dd.domains().size()
+                                                    << " realized; an unrealized domain has none)");
+      return dd.domains()[di];
+    };
+    m.def("field_convert_supported",
+          [sub](DistributedDomain &src, DistributedDomain &dst, size_t di, int64_t qsrc, int64_t qdst) {
+            return field_convert_supported(sub(src, di), qsrc, sub(dst, di), qdst);
+          },
+          py::arg("src_dd"), py::arg("dst_dd"), py::arg("domain"), py::arg("qsrc"), py::arg("qdst"));
+    m.def("field_convert",
+          [sub](DistributedDomain &src, DistributedDomain &dst, size_t di, int64_t qsrc, bool currSrc, int64_t qdst,
+                bool currDst, double scale, const Rect3 &region, uintptr_t stream, bool stats,
+                int maxBlocks) -> py::object {
+            // asynchronous without stats; with stats blocking, the scratch the destination domain's own
+            const LocalDomain &s = sub(src, di), &d = sub(dst, di);
+            hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+            FieldStats out;
+            {
+              py::gil_scoped_release r;
+              field_convert_enqueue(s, FieldRef(qsrc, currSrc), d, FieldRef(qdst, currDst), scale, region, st,
+                                    stats ? &dst.reduce_scratch(di) : nullptr, maxBlocks);
+              if (stats) {
+                if (d.backend() == Backend::Device) {
+                  d.set_device();
+                  HIP_CHECK(hipStreamSynchronize(st));
+                }
+                out = dst.reduce_scratch(di).result();
+              }
+            }
+            if (!stats) return py::none();
+            return py::cast(out);
+          },
+          py::arg("src_dd"), py::arg("dst_dd"), py::arg("domain"), py::arg("qsrc"), py::arg("curr_src"), py::arg("qdst"),
+          py::arg("curr_dst"), py::arg("scale"), py::arg("region"), py::arg("stream") = 0, py::arg("stats") = false,
+          py::arg("max_blocks") = 0);
+    m.def("field_convert_launch_info",
+          [sub](DistributedDomain &src, DistributedDomain &dst, size_t di, int64_t qsrc, bool currSrc, int64_t qdst,
+                bool currDst, double scale, const Rect3 &region, bool stats, int maxBlocks) {
+            // what field_convert would run (nothing is launched)
+            const ConvertLaunchInfo r = field_convert_launch_info(sub(src, di), FieldRef(qsrc, currSrc), sub(dst, di),
+                                                                  FieldRef(qdst, currDst), scale, region, stats, maxBlocks);
+            static const char *names[] = {"none", "host", "generic", "fast"};
+            py::dict o;
+            o["path"] = names[r.path + 1];
+            o["blocks"] = r.blocks;
+            o["items"] = r.items;
+            return o;
+          },
+          py::arg("src_dd"), py::arg("dst_dd"), py::arg("domain"), py::arg("qsrc"), py::arg("curr_src"), py::arg("qdst"),
+          py::arg("curr_dst"), py::arg("scale"), py::arg("region"), py::arg("stats") = false, py::arg("max_blocks") = 0);
+  }
+
   // ---------------- grid transfer ----------------
   m.def("grid_transfer_supported",
         [](DistributedDomain &fine, DistributedDomain &coarse, size_t di, int64_t qf, int64_t qc) {
@@ -824,6 +879,23 @@ PYBIND11_MODULE(_C, m) {
            py::arg("qy"), py::arg("curr_y"), py::arg("stats") = false, py::arg("local") = false, py::arg("stream") = 0,
            "dst = a x (qy < 0) or a x + b y over the compute region of every local sub-domain; with stats the "
            "FieldStats of the stored values (collective unless local), else None (asynchronous on `stream`)")
+      .def("convert_from",
+           [](DistributedDomain &d, DistributedDomain &src, int64_t qdst, bool currDst, int64_t qsrc, bool currSrc,
+              double scale, bool stats, bool local, uintptr_t stream) -> py::object {
+             FieldStats out;
+             {
+               py::gil_scoped_release r;
+               out = d.convert_from(src, FieldRef(qdst, currDst), FieldRef(qsrc, currSrc), scale, stats, local,
+                                    reinterpret_cast<hipStream_t>(stream));
+             }
+             if (!stats) return py::none();
+             return py::cast(out);
+           },
+           py::arg("src"), py::arg("qdst"), py::arg("curr_dst"), py::arg("qsrc"), py::arg("curr_src"),
+           py::arg("scale") = 1.0, py::arg("stats") = false, py::arg("local") = false, py::arg("stream") = 0,
+           "dst = T_dst(scale * double(src)) over the compute region of every local sub-domain, src a quantity of "
+           "another domain with the same local partition; with stats the FieldStats of the stored values (collective "
+           "unless local), else None (asynchronous on `stream`)")
       .def("reduce",
            [](DistributedDomain &d, int64_t q, py::object other, bool curr, bool otherCurr, bool local) {
              const int64_t qb = other.is_none() ? -1 : other.cast<int64_t>();

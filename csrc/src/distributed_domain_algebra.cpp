@@ -1,5 +1,6 @@
-// DistributedDomain::axpby: field linear combinations over every local sub-domain (stencil/kernels/field_axpby.hpp),
-// with the stats of the stored values merged over the sub-domains and the ranks.
+// DistributedDomain::axpby and convert_from: field linear combinations (stencil/kernels/field_axpby.hpp) and
+// type-converting copies from another domain (stencil/kernels/field_convert.hpp) over every local sub-domain, with the
+// stats of the stored values merged over the sub-domains and the ranks.
 #include "distributed_domain_impl.hpp"
 
 namespace stencil {
@@ -13,8 +14,29 @@ FieldStats DistributedDomain::axpby(FieldRef dst, double a, FieldRef x, double b
   for (size_t di = 0; di < domains_.size(); ++di)
     field_axpby_enqueue(domains_[di], dst, a, x, b, y, domains_[di].get_compute_region(), stream,
                         stats ? &reduce_scratch(di) : nullptr);
+  return stats ? merged_stats(local, stream) : FieldStats();
+}
+
+FieldStats DistributedDomain::convert_from(const DistributedDomain &srcDom, FieldRef dst, FieldRef src, double scale,
+                                           bool stats, bool local, hipStream_t stream) {
+  STENCIL_REQUIRE(realized_ && srcDom.realized(), "convert_from before realize");
+  STENCIL_REQUIRE(!stats || poisoned_.empty(), "field reduction refused after an earlier exchange failure: " << poisoned_);
+  const std::vector<LocalDomain> &from = srcDom.domains();
+  STENCIL_REQUIRE(from.size() == domains_.size(), "convert_from: " << from.size() << " local sub-domains in the source, "
+                                                                    << domains_.size() << " in the destination");
+  // every refusal before anything is enqueued
+  for (size_t di = 0; di < domains_.size(); ++di)
+    (void)field_convert_launch_info(from[di], src, domains_[di], dst, scale, domains_[di].get_compute_region(), stats);
+  for (size_t di = 0; di < domains_.size(); ++di)
+    field_convert_enqueue(from[di], src, domains_[di], dst, scale, domains_[di].get_compute_region(), stream,
+                          stats ? &reduce_scratch(di) : nullptr);
+  return stats ? merged_stats(local, stream) : FieldStats();
+}
+
+// the stats a launch per sub-domain left in the scratches: waits for `stream` on every device, merges the sub-domains
+// in index order and, unless `local`, the ranks in rank order
+FieldStats DistributedDomain::merged_stats(bool local, hipStream_t stream) {
   FieldStats mine;
-  if (!stats) return mine;
   if (backend_ == Backend::Device)
     for (const LocalDomain &d : domains_) {
       d.set_device();

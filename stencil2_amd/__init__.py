@@ -73,9 +73,10 @@ from .models.box_model import BoxStencil3D  # noqa: E402,F401
 from .models.varcoef_model import VarCoefStencil3D  # noqa: E402,F401
 from .models.star_cg import StarCG  # noqa: E402,F401
 from .models.multigrid import StarMG  # noqa: E402,F401
+from .models.star_pcg import StarPCG  # noqa: E402,F401
 
 __all__ = [
     "Backend", "Boundary", "BoundaryConditions", "FaceCondition", "FaceKind", "Dim3", "DType", "MethodFlags", "PlacementStrategy", "Radius", "Rect3", "Statistics", "StencilKind",
-    "DistributedDomain", "Jacobi3D", "AstarothSim", "StencilModel", "StarStencil3D", "BoxStencil3D", "VarCoefStencil3D", "StarCG", "StarMG", "init_process_group", "get_group",
+    "DistributedDomain", "Jacobi3D", "AstarothSim", "StencilModel", "StarStencil3D", "BoxStencil3D", "VarCoefStencil3D", "StarCG", "StarMG", "StarPCG", "init_process_group", "get_group",
     "TransportOptions", "build_info", "RankPartition", "NodePartition", "TrivialPlacement", "NodeAwarePlacement", "qap_solve", "qap_solve_catch",
 ]

@@ -214,6 +214,10 @@ class StarMG:
         if not self._varcoef:
             raise ValueError("set_kappa belongs to VarCoefWeights")
         self._dds[0].fill_from_global(self.kappa, fn)
+        return self._coarsen_kappa()
+
+    def _coarsen_kappa(self):
+        """level 0's kappa is set: the coarser levels' means, then every level's halos and ghost cells"""
         for l in range(1, self.levels):
             fine, coarse = self._dds[l - 1], self._dds[l]
             for di in range(fine.num_domains()):

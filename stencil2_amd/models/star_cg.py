@@ -126,10 +126,11 @@ class StarCG:
         self.u, self.r, self.p, self.f = (dd.add_data(n, self.dtype) for n in ("u", "r", "p", "f"))
         # the coefficient comes after u, r, p, f, so their indices are the same for every kind of weights
         self.kappa = dd.add_data("kappa", self.dtype) if self._varcoef else None
+        more_open = tuple(self._add_quantities(dd))
         if boundary is not None:
             dd.set_boundary_conditions(boundary)
             dd.set_boundary_conditions(self.p, _conditions(boundary, True))
-            for q in (self.r, self.f):
+            for q in (self.r, self.f) + more_open:
                 dd.set_boundary_conditions(q, _conditions(boundary, False, all_open=True))
             if self._varcoef:
                 dd.set_boundary_conditions(self.kappa, kappa_conditions(boundary, kappa_boundary))
@@ -150,6 +151,10 @@ class StarCG:
             if boundary is not None:
                 dd.apply_boundary(self.kappa)
         self.set_guess()
+
+    def _add_quantities(self, dd):
+        """a subclass adds its quantities here, after u, r, p, f (and kappa), and returns those that take Open faces"""
+        return ()
 
     def _zero(self, gz, gy, gx):
         return torch.zeros((), dtype=self.dtype, device=gz.device) * (gz + gy + gx)

@@ -190,6 +190,47 @@ def field_axpby_supported(dd, di: int, dst: int, x: int, y=None) -> bool:
     return _C.field_axpby_supported(getattr(dd, "native", dd), di, int(dst), int(x), -1 if y is None else int(y))
 
 
+def _convert_args(src_dd, dst_dd, di, region):
+    src, dst = getattr(src_dd, "native", src_dd), getattr(dst_dd, "native", dst_dd)
+    if region is None:
+        region = dst.domain(di).get_compute_region()
+    return src, dst, region
+
+
+def field_convert(src_dd, dst_dd, di: int, src: int, dst: int, scale: float = 1.0, src_curr: bool = True,
+                  dst_curr: bool = True, region=None, stream: int = 0, stats: bool = False, max_blocks: int = 0):
+    """dst(region) = T_dst(scale * double(src)): quantity `src` of local sub-domain di of `src_dd` into quantity `dst`
+    of sub-domain di of `dst_dd`, fp32 or fp64 on each side. One product in double and one conversion to the
+    destination type, so the result is bitwise equal to `convert_reference`; scale = 1 is an exact cast. The two
+    domains (which may be the same object) are on one backend and device and give sub-domain di the same compute
+    region; radii, pitches and padding may differ. `*_curr` pick each side's curr or next buffer and `region` (global
+    coordinates) defaults to the compute region. Only cells of the region are written, so the halos of dst are stale
+    afterwards. Asynchronous on `stream` and returns None; with `stats` it waits for the stream and returns the
+    FieldStats of the stored values from the same pass, as `field_axpby` does. `max_blocks`: 0 = one round of
+    resident blocks, else exactly that many (csrc/src/kernels/field_convert.hip)."""
+    s, d, region = _convert_args(src_dd, dst_dd, di, region)
+    return _C.field_convert(s, d, di, int(src), bool(src_curr), int(dst), bool(dst_curr), float(scale), region, stream,
+                            bool(stats), max_blocks)
+
+
+def field_convert_launch_info(src_dd, dst_dd, di: int, src: int, dst: int, scale: float = 1.0, src_curr: bool = True,
+                              dst_curr: bool = True, region=None, stats: bool = False, max_blocks: int = 0) -> dict:
+    """What `field_convert` would run for these arguments (nothing is launched; the same refusals raise): `path`
+    ("fast": the row kernel when both sides are in the aligned vector layout, "generic": one thread per cell, "host",
+    "none": empty region), `blocks` of the launch and `items`, the (row, plane) pairs of the region."""
+    s, d, region = _convert_args(src_dd, dst_dd, di, region)
+    return _C.field_convert_launch_info(s, d, di, int(src), bool(src_curr), int(dst), bool(dst_curr), float(scale),
+                                        region, bool(stats), max_blocks)
+
+
+def field_convert_supported(src_dd, dst_dd, di: int, src: int, dst: int) -> bool:
+    """True when `field_convert` takes quantity `src` of `src_dd` and `dst` of `dst_dd` for local sub-domain di: fp32 /
+    fp64 quantities (or opaque 4- / 8-byte elements) of realized domains on one backend and device with the same
+    compute region."""
+    return _C.field_convert_supported(getattr(src_dd, "native", src_dd), getattr(dst_dd, "native", dst_dd), di,
+                                      int(src), int(dst))
+
+
 def _fill_args(dd, q, bc):
     """(native, quantities, conditions): q None = every quantity whose conditions fill a face, as apply_boundary()"""
     native = getattr(dd, "native", dd)

@@ -256,6 +256,13 @@ def axpby_reference(a, x: torch.Tensor, b=None, y=None) -> torch.Tensor:
     return t + s
 
 
+def convert_reference(x: torch.Tensor, scale=1.0, dtype=None) -> torch.Tensor:
+    """dtype(scale * double(x)): the oracle of `field_convert`. One product in double, then one conversion to `dtype`
+    (default x's): round to nearest even, overflow to +-inf, subnormals kept. scale = 1 is an exact cast."""
+    t = torch.tensor(float(scale), dtype=torch.float64).to(x.device) * x.double()
+    return t.to(x.dtype if dtype is None else dtype)
+
+
 # ---- physical boundary conditions (csrc/include/stencil/core/boundary.hpp) ----
 _FACES = ((0, (-1, 0, 0), (1, 0, 0)), (1, (0, -1, 0), (0, 1, 0)), (2, (0, 0, -1), (0, 0, 1)))  # axis, low dir, high dir
 
@@ -477,5 +484,75 @@ def varcoef_mg_cycle_reference(u: torch.Tensor, f: torch.Tensor, kappa: torch.Te
     return cycle(0, u, f, kappa, bc)
 
 
+def mgpcg_reference(u0: torch.Tensor, f: torch.Tensor, weights_per_level, bc, kappa=None, kappa_bc=None,
+                    precond_dtype=None, nu=(2, 2), omega: float = 6.0 / 7.0, coarse_sweeps: int = 32, tol: float = 1e-8,
+                    max_iters: int = 200, flexible: bool = True):
+    """The algorithm of `models.StarPCG.solve` on gathered global (z, y, x) grids: conjugate gradients on
+    `weights_per_level[0]` (under `bc`; the search direction under its homogeneous twin) preconditioned by one V-cycle
+    from 0 (`mg_cycle_reference`, or `varcoef_mg_cycle_reference` with `kappa`) under the homogeneous conditions. The
+    cycle runs in `precond_dtype` (None: f's): z = convert(cycle(0, convert(r, 1 / s)), s) with s = ||r||2 and, for
+    VarCoefWeights, the coefficient `convert_reference(kappa, 1, precond_dtype)`. flexible: beta = -alpha (z . Ap) /
+    rho_old (Polak-Ribiere), else rho / rho_old. Fields are in f's dtype through `axpby_reference`; every scalar is a
+    torch double sum. Returns (u, history), history the recursive ||r||2 / ||f||2 after every iteration. The yardstick
+    of the convergence tests; not bitwise (the solver's reductions sum in another order)."""
+    from .. import _C
+    from ..models.star_cg import _conditions
+    from ..models.varcoef_model import kappa_conditions
+
+    A = weights_per_level[0]
+    od = f.dtype
+    pd = od if precond_dtype is None else precond_dtype
+    hom = None if bc is None else _conditions(bc, True)
+    varcoef = isinstance(A, _C.VarCoefWeights)
+    if varcoef:
+        kbc = None if bc is None else kappa_conditions(bc, kappa_bc)
+        kp = convert_reference(kappa, 1.0, pd)
+
+    def apply(v, cond):
+        if varcoef:
+            return varcoef_step_reference(v, kappa, A, boundary=cond, kappa_boundary=kbc)
+        step = box_step_reference if isinstance(A, _C.BoxWeights) else star_step_reference
+        return step(v, A, boundary=cond)
+
+    def dot(a, b):
+        return float((a.double() * b.double()).sum())
+
+    def precondition(r, s):
+        g = convert_reference(r, 1.0 / s, pd)
+        if varcoef:
+            e = varcoef_mg_cycle_reference(torch.zeros_like(g), g, kp, weights_per_level, hom, kappa_bc, nu, omega,
+                                           coarse_sweeps)
+        else:
+            e = mg_cycle_reference(torch.zeros_like(g), g, weights_per_level, hom, nu, omega, coarse_sweeps)
+        return convert_reference(e, s, od)
+
+    history = []
+    ff = dot(f, f)
+    if ff == 0:
+        return torch.zeros_like(f), history
+    u = u0.clone()
+    r = axpby_reference(1.0, f, -1.0, apply(u, bc))
+    rr = dot(r, r)
+    if max_iters <= 0 or math.sqrt(rr / ff) < tol:
+        return u, history
+    z = precondition(r, math.sqrt(rr))
+    rho = dot(r, z)
+    p = z.clone()
+    while True:
+        Ap = apply(p, hom)
+        alpha = rho / dot(p, Ap)
+        u = axpby_reference(1.0, u, alpha, p)
+        r = axpby_reference(1.0, r, -alpha, Ap)
+        rr = dot(r, r)
+        history.append(math.sqrt(rr / ff))
+        if len(history) >= max_iters or history[-1] < tol:
+            return u, history
+        z = precondition(r, math.sqrt(rr))
+        rho_new = dot(r, z)
+        beta = -alpha * dot(z, Ap) / rho if flexible else rho_new / rho
+        p = axpby_reference(1.0, z, beta, p)
+        rho = rho_new
+
+
 __all__ = ["periodic_gather", "jacobi_spheres", "jacobi_step_reference", "astaroth_step_reference",
-           "astaroth_init_reference", "star_step_reference", "box_step_reference", "varcoef_step_reference", "varcoef_relax_reference", "varcoef_mg_cycle_reference", "axpby_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]
+           "astaroth_init_reference", "star_step_reference", "box_step_reference", "varcoef_step_reference", "varcoef_relax_reference", "varcoef_mg_cycle_reference", "axpby_reference", "convert_reference", "mgpcg_reference", "restrict_reference", "prolong_reference", "mg_cycle_reference", "pad_reference", "boundary_fill_reference", "math"]

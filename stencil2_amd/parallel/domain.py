@@ -117,6 +117,16 @@ class DistributedDomain:
         """q = a * q over the compute regions, in place"""
         self.axpby(q, a, q, dst_curr=curr, x_curr=curr)
 
+    def convert_from(self, src_dd, dst_q: int, src_q: int, scale: float = 1.0, dst_curr: bool = True,
+                     src_curr: bool = True, stats: bool = False, local: bool = False, stream: int = 0):
+        """dst_q = T_dst(scale * double(src_q)) over the compute region of every local sub-domain, src_q a quantity of
+        `src_dd`: another domain with the same local partition (or this one), fp32 or fp64 on each side
+        (`ops.field_convert`). Asynchronous and not collective, returns None; with `stats` it waits for the stream and
+        returns the FieldStats of the stored values: collective unless `local`, identical bits on every rank. Only the
+        compute region is written, so the halos of dst_q are stale: exchange before the next stencil."""
+        return self._dd.convert_from(getattr(src_dd, "native", src_dd), int(dst_q), bool(dst_curr), int(src_q),
+                                     bool(src_curr), float(scale), bool(stats), bool(local), stream)
+
     def fill_from_global(self, q: int, fn, include_halo: bool = False):
         """Set every local cell of quantity q to fn(gz, gy, gx) (torch index tensors of global coordinates)."""
         for di, d in enumerate(self.domains()):

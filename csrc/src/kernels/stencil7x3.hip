@@ -613,10 +613,12 @@ stencil7x3_xh_kernel(StencilArgs<T> a, ZPartBounds zbounds) {
 template <int KIND, bool PUB, bool NT>
 __global__ __launch_bounds__(64 * 12, 3) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
-  constexpr int NW = 12;     // 3 waves per SIMD (168 VGPRs), 3 x 48 KiB of LDS
+  constexpr int NW = 12;     // 3 waves per SIMD (a cap of 168 VGPRs; the Jacobi instance uses 137, Astaroth 121), 3 x 48 KiB of LDS
   using T = float;
   using NV = nf4;
   constexpr int V = 4, H = 2;
+  // (a lane owning 8 consecutive cells needs no wrap selects and 12 % fewer VALU instructions per step, and measured
+  // 10 % slower: every 16-B load and store then touches half of each 32 B; BASELINE.md, "VALU diet")
   constexpr int CS = 64 * V; // cells between a lane's chunks (chunk h = cells 256 h + 4 lane ..)
   constexpr int LS = V;      // cells between adjacent lanes
   constexpr int YO = NW - 6; // output rows per block
@@ -646,7 +648,8 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
   // The wave's role = the levels its row computes (wave-uniform): 0 on rows 0 / 11 (source rows only), 1 (u1) on 1 /
   // 10, 2 (u1, u2) on 2 / 9, 3 (u1, u2, u3 = output) on 3..8. The whole march is instantiated per role, and the
   // warm-up steps (fewer valid levels) are unrolled separately, so the steady-state step has no role or level
-  // branches: per step one tiny-sum test (ballot) and, for Jacobi, one sphere test per level.
+  // branches: per step one tiny-sum test per level (a compare and a branch over the row's 8 sums; never taken on
+  // ordinary data) and, for Jacobi, one sphere test per level.
   auto body = [&](auto roleTag) {
     constexpr int R = decltype(roleTag)::value;
     bool odd = sg.odd;
@@ -723,6 +726,7 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
           // array (scratch stores + loads on every row update, 449 vs 304 us per triple)
           const T r30 = rot_prev(cm[0][V - 1]), r31 = rot_prev(cm[1][V - 1]);
           const T l00 = rot_next(cm[0][0]), l01 = rot_next(cm[1][0]);
+          NV s6[H];
 #pragma unroll
           for (int h = 0; h < H; ++h) {
             const T left = h == 0 ? (lane0 ? r31 : r30) : (lane0 ? r30 : r31);
@@ -733,7 +737,16 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
               vpx[k] = k < V - 1 ? cm[h][k + 1] : right;
               vmx[k] = k > 0 ? cm[h][k - 1] : left;
             }
-            o[h] = div6v<T, NV, V>(sum6v<T, KIND>(vpx, vmx, dn[h], up[h], zp[h], zm[h]));
+            s6[h] = sum6v<T, KIND>(vpx, vmx, dn[h], up[h], zp[h], zm[h]);
+          }
+          // one tiny-sum test per row update (div6v tests per chunk): both chunks' quotients first, then one branch
+          // over all 8 sums, which no wave normally enters
+          float m = 1.0f; // any value >= 2^-100
+#pragma unroll
+          for (int h = 0; h < H; ++h) o[h] = div6v_fast<NV, V>(s6[h], m);
+          if (__builtin_expect(m < 0x1p-100f, 0)) {
+#pragma unroll
+            for (int h = 0; h < H; ++h) div6v_fix<NV, V>(s6[h], o[h]);
           }
           return T(1);
         };
@@ -769,7 +782,6 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
             }
             __syncthreads();
           }
-          int buf = 0;
           int t = -4;
           // one z step with LV = min(role, levels valid at this step) levels
           auto step = [&](auto phase, auto lvTag) -> bool {
@@ -778,6 +790,9 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
             // slots: s0 = plane z+dz, s1 = z+2dz, s2 = z+3dz; sn receives z + NC dz (it held plane z)
             constexpr int s0 = k % NC, s1 = (k + 1) % NC, s2 = (k + 2) % NC, sn = (k + NC - 1) % NC;
             if (t >= nzs) return false;
+            // the LDS buffer a step reads is its phase's parity (t = -4 runs phase 0 on buffer 0, every step flips,
+            // the loop has 4 phases), so every LDS address is a per-segment VGPR plus an immediate offset
+            constexpr int buf = k & 1;
             const int z = z0 + t * dz;
             load_row(z + NC * dz, sn);
             NV o[H];
@@ -852,7 +867,6 @@ stencil7x3_wrap_kernel(StencilArgs<float> a, ZPartBounds zbounds) {
                   (unsigned long long)(min(YO, a.hiy - yblk)) * (unsigned long long)(a.hix - a.lox);
               __hip_atomic_fetch_add(a.pub, cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
-            buf = nbuf;
 #pragma unroll
             for (int h = 0; h < H; ++h) {
               U1b[h] = U1c[h];

@@ -95,6 +95,23 @@ template <typename T, typename X, int N> __device__ __forceinline__ X div6v(cons
   }
 }
 
+// div6v in two parts, for callers that test once for several vectors (fp32): div6v_fast is the two-FMA quotient alone
+// and folds min |s| into m (start m at any value >= 2^-100); where m ends below 2^-100, div6v_fix replaces the
+// quotients of the tiny sums by the true division, as div6v's branch does
+template <typename X, int N> __device__ __forceinline__ X div6v_fast(const X &s, float &m) {
+  const X c = X(1.0f / 6.0f), six = X(6.0f);
+  const X q0 = s * c;
+  const X r = __builtin_elementwise_fma(-q0, six, s);
+#pragma unroll
+  for (int e = 0; e < N; ++e) m = __builtin_fminf(m, __builtin_fabsf(s[e]));
+  return __builtin_elementwise_fma(r, c, q0);
+}
+template <typename X, int N> __device__ __forceinline__ void div6v_fix(const X &s, X &q) {
+#pragma unroll
+  for (int e = 0; e < N; ++e)
+    if (__builtin_fabsf(s[e]) < 0x1p-100f && s[e] != 0.0f) q[e] = s[e] / 6.0f;
+}
+
 // calls f(integral_constant<I>) for I = 0, 1, ... while it returns true; true if all did
 template <typename F, int... I> __device__ __forceinline__ bool run_phases(F &f, std::integer_sequence<int, I...>) {
   return (f(std::integral_constant<int, I>{}) && ...);
